@@ -10,10 +10,26 @@ LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or -- when WORLD_SIZE is
 script starts N rank processes itself BEFORE anything touches the GPU and relays rank 0's JSON line.
 A WORLD_SIZE that contradicts --gpus is an error (exit 2), never a relabelled single-GPU number.
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live: every MFMA conv launch of one extra
-(untimed) step is bracketed with HIP events on the launch stream; `cpu_baseline` times the oracle's
-stock-torch port (oracle/torch_unet.py) on the host cores for a bounded sample (rank 0, N=1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line;
+`ms_per_step` is the wall-clock mean of one timed step.
 
+  --full                     also the side measurements (each takes runs of its own): `roofline` -- every
+                             MFMA conv launch of one extra (untimed) step bracketed with HIP events on the
+                             launch stream; `pcie_inclusive` and `parity_mode` (N=1 only); `cpu_baseline`,
+                             the oracle's stock-torch port (oracle/torch_unet.py) on the host cores for a
+                             bounded sample (rank 0, N=1 only).  --no-h2d / --no-parity-mode /
+                             --no-cpu-baseline drop single legs of it.  Without --full they are null.
+  --dump-outputs DIR         after the timed steps, rank 0 writes what the last timed step produced:
+                             DIR/loss.npy, params.npy (every parameter after the optimizer update, flattened
+                             in named_parameters() order), grads.npy (the step's gradients, same order) and
+                             buffers.npy (floating-point buffers: BN running statistics), float32, 64 MB at
+                             most in all (a larger array becomes a fixed, seeded sample of its elements).
+                             Inputs and initial weights are seeded, and with this option the parameters,
+                             buffers and optimizer state are put back to their seeded values just before the
+                             last timed step (class Rewind), so that step reads the same inputs every run: the
+                             steps before it chain a state that the weight gradients' fp32 atomics make differ
+                             in the last bits from run to run, and training amplifies that.  Two runs then
+                             differ by the rounding of one step's atomic sums only.
   --backend gloo --dry-run   no kernels, CPU tensors: rendezvous, parameter/buffer broadcast, the
                              bucketed reducer on the real flat-parameter layout, barrier, MAX-reduce and
                              the JSON line (tests/test_ddp_cpu.py runs it with --gpus 2).
@@ -120,7 +136,91 @@ def parse_args(argv=None):
     ap.add_argument("--depth", type=int, default=64, help="cfg5: slices per volume")
     ap.add_argument("--graph", action="store_true",
                     help="replay forward+loss+backward as one HIP graph (no gain at batch 32: the queue never runs dry)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: roofline (one event-bracketed extra step), PCIe-inclusive rate, "
+                         "fp32 parity-mode rate, CPU baseline (cfg2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss / parameters / gradients / buffers as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the real kernels (not --dry-run)")
+    return args
+
+
+# ---------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+NPY_HEADER_SLACK = 4096
+
+
+class Rewind:
+    """The seeded start state of the training loop (parameters, buffers, optimizer state), put back in place before the
+    last timed step when outputs are dumped.  Steps chain their state, and the fp32 atomics that sum weight gradients
+    differ in the last bit from run to run, so the state the loop reaches after a few steps is not reproducible;
+    rewound, the last step reads the same inputs every run.  One device copy of the state: nothing the step time
+    notices."""
+
+    def __init__(self, model, opt):
+        import torch
+        self.opt = opt
+        flat = getattr(opt, "flat_p", None)         # FusedSGD: every parameter is a view of one flat buffer
+        self.tensors = ([flat] if flat is not None else list(model.parameters())) + list(model.buffers())
+        with torch.no_grad():
+            self.saved = [t.detach().clone() for t in self.tensors]
+
+    def __call__(self):
+        import torch
+        from retinal_oct_image_segmentation_via_deep_learning_amd import _lib
+        with torch.no_grad():
+            for t, s in zip(self.tensors, self.saved):
+                t.copy_(s)
+        if hasattr(self.opt, "flat_p"):
+            if self.opt.buf is not None:
+                self.opt.buf.zero_()
+            self.opt.steps = 0
+        else:
+            self.opt.state.clear()
+        _lib.param_generation[0] += 1               # packed-weight caches must notice the restored parameters
+
+
+def step_outputs(model, loss):
+    """What a caller of the training step receives from its last call: the loss vector, the updated parameters, the
+    gradients the update used and the BN running statistics -- host float32 arrays."""
+    import torch
+    with torch.no_grad():
+        params = list(model.parameters())
+        out = {"loss": loss.detach().reshape(-1).float().cpu().numpy(),
+               "params": torch.cat([p.reshape(-1).float() for p in params]).cpu().numpy()}
+        grads = [p.grad for p in params if p.grad is not None]
+        if grads:
+            out["grads"] = torch.cat([g.reshape(-1).float() for g in grads]).cpu().numpy()
+        bufs = [b for b in model.buffers() if b.is_floating_point()]
+        if bufs:
+            out["buffers"] = torch.cat([b.reshape(-1).float() for b in bufs]).cpu().numpy()
+    return out
+
+
+def write_outputs(dirpath, arrays):
+    """DIR/<name>.npy for every array, DUMP_BUDGET_BYTES in all.  Smaller arrays are written whole first; an array
+    larger than its share of what is left becomes a sample of its flattened elements at sorted indices drawn by
+    numpy.random.default_rng(0) -- a function of the array's size and share only, so two builds keep the same
+    elements."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    left = DUMP_BUDGET_BYTES - NPY_HEADER_SLACK * len(arrays)
+    order = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, name in enumerate(order):
+        a = np.ascontiguousarray(arrays[name])
+        keep = min(a.size, (left // (len(order) - i)) // a.itemsize)
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+            print(f"bench.py: {name}.npy holds a seeded sample of {keep} of {arrays[name].size} elements", file=sys.stderr)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        left -= a.nbytes
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -344,6 +444,7 @@ def side_config(args) -> int:
         t = torch.randint(0, 2, (b, h, w), generator=g).to(dev)
         trainer = ddp.DataParallelTrainer(model, lr=0.01, momentum=0.9, use_graph=args.graph,
                                           graph_warmup=max(1, min(2, args.warmup - 1)))
+        opt = trainer.opt
         flops = bionet_train_flops(2, h, w)
         unit, workload = "B-scans/s", (f"SOTAS/Layers_Segment BioNet_2020.UNet(1,2) train step, {h}x{w}, batch {b} "
                                       f"(BASELINE configs[0], the reference's own CPU-runnable case)")
@@ -425,14 +526,19 @@ def side_config(args) -> int:
         # the autograd-driven block families take ~8 steps to reach their steady state (caching allocator, per-shape weight
         # packing): with 3 warm-up steps mgunet2 read 600 B-scans/s for a steady 850; the line reports the count used
         args.warmup = 8
+    rewind = Rewind(model, opt) if args.dump_outputs else None
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if rewind is not None and i == args.steps - 1:
+            rewind()
         loss = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, step_outputs(model, loss))
     value = b * args.steps / elapsed
     achieved = value * flops / 1e12
     print(json.dumps({
@@ -516,6 +622,39 @@ def parity_mode_rate(args, dev, x, t):
     return out
 
 
+def conv_roofline(args, trainer, model, x, t, value, world):
+    """Roofline of the MFMA conv stack: one extra (untimed) step with HIP events around every conv launch."""
+    import torch
+    flops_bscan = train_flops(args.features, args.classes, args.height, args.width)
+    trainer.graph = None                # the measuring step below runs eagerly
+    trainer.use_graph = False
+    model._engine.prof = []
+    trainer.step(x, t)
+    torch.cuda.synchronize()
+    prof = model._engine.prof
+    model._engine.prof = None
+    conv_ms = sum(s.elapsed_time(e) for _, s, e in prof)
+    kinds = {}
+    for k, s, e in prof:
+        kinds.setdefault(k, [0, 0.0])
+        kinds[k][0] += 1
+        kinds[k][1] += s.elapsed_time(e)
+    achieved = flops_bscan * args.batch / (conv_ms * 1e-3) / 1e12
+    traffic, traffic_source = traffic_from_profile(args, len(prof))
+    roofline = {
+        "bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+        "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
+        "kernel": "igemm2_kernel + wgrad2_kernel + first_fprop_mfma_kernel + first_wgrad_mfma_kernel (conv stack: every "
+                  "convolution / transposed convolution launch of the step except the 1x1 head, %d launches/step)" % len(prof),
+        "avg_launch_ms": round(conv_ms / max(len(prof), 1), 4),
+        "flop_per_launch": flops_bscan * args.batch / max(len(prof), 1),
+        "conv_ms_per_step": round(conv_ms, 3),
+        "by_kernel_ms": {k: [v[0], round(v[1], 3)] for k, v in kinds.items()},
+        "whole_step_frac": round(value / world * flops_bscan / 1e12 / PEAK_BF16_TFLOPS, 4),
+    }
+    return roofline
+
+
 def worker(args) -> int:
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if world_env != args.gpus:
@@ -559,11 +698,14 @@ def worker(args) -> int:
             ddp.barrier(local)
         torch.cuda.synchronize()
 
+    rewind = Rewind(model, trainer.opt) if args.dump_outputs else None
     for _ in range(args.warmup):
         trainer.step(x, t)
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if rewind is not None and i == args.steps - 1:
+            rewind()
         loss = trainer.step(x, t)
     sync()
     elapsed = time.perf_counter() - t0
@@ -577,49 +719,24 @@ def worker(args) -> int:
         elapsed = tt.item()
     ms_per_step = elapsed / args.steps * 1e3
     value = args.batch * world * args.steps / elapsed
+    graph_used = trainer.graph is not None
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, step_outputs(model, loss))
 
-    # ---- roofline of the MFMA conv stack: one extra step with events around every conv launch ----
-    flops_bscan = train_flops(args.features, args.classes, args.height, args.width)
-    graph_used, trainer.graph = trainer.graph is not None, None     # the measuring step below runs eagerly
-    trainer.use_graph = False
-    model._engine.prof = []
-    trainer.step(x, t)
-    torch.cuda.synchronize()
-    prof = model._engine.prof
-    model._engine.prof = None
-    conv_ms = sum(s.elapsed_time(e) for _, s, e in prof)
-    kinds = {}
-    for k, s, e in prof:
-        kinds.setdefault(k, [0, 0.0])
-        kinds[k][0] += 1
-        kinds[k][1] += s.elapsed_time(e)
-    achieved = flops_bscan * args.batch / (conv_ms * 1e-3) / 1e12
-    traffic, traffic_source = traffic_from_profile(args, len(prof))
-    roofline = {
-        "bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-        "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
-        "kernel": "igemm2_kernel + wgrad2_kernel + first_fprop_mfma_kernel + first_wgrad_mfma_kernel (conv stack: every "
-                  "convolution / transposed convolution launch of the step except the 1x1 head, %d launches/step)" % len(prof),
-        "avg_launch_ms": round(conv_ms / max(len(prof), 1), 4),
-        "flop_per_launch": flops_bscan * args.batch / max(len(prof), 1),
-        "conv_ms_per_step": round(conv_ms, 3),
-        "by_kernel_ms": {k: [v[0], round(v[1], 3)] for k, v in kinds.items()},
-        "whole_step_frac": round(value / world * flops_bscan / 1e12 / PEAK_BF16_TFLOPS, 4),
-    }
+    roofline = pcie = parity = cpu = None
+    if args.full:
+        roofline = conv_roofline(args, trainer, model, x, t, value, world)
 
-    pcie = None
-    if world == 1 and not args.no_h2d:
-        pcie = pcie_inclusive(args, trainer, x, t)
+        if world == 1 and not args.no_h2d:
+            pcie = pcie_inclusive(args, trainer, x, t)
 
-    # the precision the parity contract is stated in (arg-max identical / Dice within 1e-5: fp32 storage, exact fp32 MFMA):
-    # the same step, a few iterations, so that its cost is visible next to the bf16 headline
-    parity = None
-    if world == 1 and not args.no_parity_mode:
-        parity = parity_mode_rate(args, dev, x, t)
+        # the precision the parity contract is stated in (arg-max identical / Dice within 1e-5: fp32 storage, exact fp32
+        # MFMA): the same step, a few iterations, so that its cost is visible next to the bf16 headline
+        if world == 1 and not args.no_parity_mode:
+            parity = parity_mode_rate(args, dev, x, t)
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(args)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(args)
 
     if rank == 0:
         out = {
@@ -640,7 +757,7 @@ def worker(args) -> int:
                        "grad_buckets_bytes": [4 * (hi - lo) for _, lo, hi in trainer.reducer.buckets],
                        "hip_graph": graph_used, "hip_graph_error": trainer.graph_error},
             "loss": float(loss[0].item()),
-            "roofline": roofline, "cpu_baseline": cpu, "pcie_inclusive": pcie, "parity_mode": parity,
+            "full": args.full, "roofline": roofline, "cpu_baseline": cpu, "pcie_inclusive": pcie, "parity_mode": parity,
         }
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,9 +1,10 @@
 #!/bin/bash
 # usage (on the GPU box): tools/kstats.sh TAG [pattern]  -> per-kernel average durations of a 3-step bench run
 TAG=$1; PAT=${2:-.}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$GRAFT_REPO_ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_$TAG -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-h2d --no-parity-mode > $O/ks_$TAG.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_$TAG -- python3 $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-h2d --no-parity-mode > $O/ks_$TAG.log 2>&1
 cd $GRAFT_REPO_ROOT
 python3 - "$O/ks_$TAG" "$PAT" <<'PY'
 import csv, glob, re, sys
