@@ -106,18 +106,19 @@ class Attention_block(nn.Module):
 
 
 class _SDNet(nn.Module):
-    def __init__(self, img_ch, output_ch, channels, gates, head_in):
+    def __init__(self, img_ch, output_ch, channels, gates, head_in, act=nn.ReLU, drop_rate=0.0):
         super().__init__()
         self._n = len(channels)
+        kw = dict(act=act, drop_rate=drop_rate)
         self.Maxpool = nn.MaxPool2d(2, 2)
-        self.Conv1 = conv_block(img_ch, channels[0])
+        self.Conv1 = conv_block(img_ch, channels[0], **kw)
         for i in range(1, self._n):
-            setattr(self, f"Conv{i + 1}", conv_block(channels[i - 1], channels[i]))
+            setattr(self, f"Conv{i + 1}", conv_block(channels[i - 1], channels[i], **kw))
         for i in range(self._n, 1, -1):
-            setattr(self, f"Up{i}", up_conv(channels[i - 1], channels[i - 2]))
+            setattr(self, f"Up{i}", up_conv(channels[i - 1], channels[i - 2], **kw))
             if gates:
                 setattr(self, f"Att{i}", Attention_block(channels[i - 2], channels[i - 2], channels[i - 2] // 2))
-            setattr(self, f"Up_conv{i}", conv_block(channels[i - 1], channels[i - 2]))
+            setattr(self, f"Up_conv{i}", conv_block(channels[i - 1], channels[i - 2], **kw))
         self.Conv_1x1 = nn.Conv2d(head_in, output_ch, 1)
         self._gates = gates
 
@@ -137,18 +138,18 @@ class _SDNet(nn.Module):
 
 
 class U_Net(_SDNet):
-    def __init__(self, img_ch=3, output_ch=1, channels=(64, 128, 256, 512, 1024)):
-        super().__init__(img_ch, output_ch, list(channels), False, 64)
+    def __init__(self, img_ch=3, output_ch=1, channels=(64, 128, 256, 512, 1024), act_func=None, drop_rate=0.0):
+        super().__init__(img_ch, output_ch, list(channels), False, 64, act_func or nn.ReLU, drop_rate)
 
 
 class AttU_Net(_SDNet):
-    def __init__(self, img_ch=1, output_ch=1, channels=(64, 128, 256, 512, 1024)):
-        super().__init__(img_ch, output_ch, list(channels), True, channels[0])
+    def __init__(self, img_ch=1, output_ch=1, channels=(64, 128, 256, 512, 1024), act=None, drop_rate=0.0):
+        super().__init__(img_ch, output_ch, list(channels), True, channels[0], act or nn.ReLU, drop_rate)
 
 
 class AttU_Net4(_SDNet):      # SD_Layer_Net/unet.py:153-214: four levels
-    def __init__(self, img_ch=1, output_ch=1, channels=(64, 128, 256, 512)):
-        super().__init__(img_ch, output_ch, list(channels), True, channels[0])
+    def __init__(self, img_ch=1, output_ch=1, channels=(64, 128, 256, 512), act=None, drop_rate=0.0):
+        super().__init__(img_ch, output_ch, list(channels), True, channels[0], act or nn.ReLU, drop_rate)
 
 
 # ---- MGU-Net: /root/reference/SOTAS/Layers_Segment/MGUNet_2021.py:29-39 (Basconv), :110-148 (GloRe_Unit), :150-194 (MGR_Module),

@@ -152,8 +152,8 @@ def init_weights(net, init_type="normal"):
 # ------------------------------------------------------------------------------------------------
 # act != nn.ReLU / Dropout2d(p > 0) (common.py:7,13,17,29,34): the GENERAL schedule -- convolutions and BatchNorm on the HIP
 # kernels with nothing deferred, Dropout2d (ops.dropout2d) and the activation module the constructor made (`act()`, as the
-# reference does) applied to the materialised NHWC tensor.  The activation must therefore be elementwise; the ones that look
-# at a dimension are refused.  nn.ReLU without dropout keeps the fused / deferred schedule.
+# reference does) applied to the materialised NHWC tensor's fp32 view and rounded once (_act).  The activation must therefore
+# be elementwise; the ones that look at a dimension are refused.  nn.ReLU without dropout keeps the fused / deferred schedule.
 _DIM_ACTS = (nn.Softmax, nn.Softmax2d, nn.LogSoftmax, nn.Softmin, nn.GLU, nn.Threshold, nn.MultiheadAttention)
 
 
@@ -162,6 +162,12 @@ def _check_act(act):
         raise TypeError("act must be an nn.Module class constructed without arguments (the reference calls act())")
     if issubclass(act, _DIM_ACTS):
         raise NotImplementedError(f"act={act.__name__} is not elementwise: not on the HIP path")
+
+
+def _act(mod: nn.Module, a):
+    """The block's activation module on the fp32 view of a materialised NHWC tensor, rounded once to its dtype: a
+    parameterised activation (nn.PReLU: fp32 weight) neither promotes nor meets a bf16 operand, and its weight gets a gradient."""
+    return mod(a.float()).to(a.dtype)
 
 
 class conv_block(HipModule):
@@ -188,9 +194,9 @@ class conv_block(HipModule):
         if not self._relu or _drops(self):   # general schedule (see _check_act)
             i = ops.conv_bn_act(dt, a, self.init_conv, x1=a1)
             t = ops.conv_bn_act(dt, i, self.conv[0], self.conv[1])
-            t = self.conv[3](ops.dropout2d(t, self.conv[2].p, self.conv[2].training))
+            t = _act(self.conv[3], ops.dropout2d(t, self.conv[2].p, self.conv[2].training))
             u = ops.conv_bn_act(dt, t, self.conv[4], self.conv[5])
-            return self.activation(ops.dropout2d(u, self.conv[6].p, self.conv[6].training) + i)
+            return _act(self.activation, ops.dropout2d(u, self.conv[6].p, self.conv[6].training) + i)
         # init_conv's bias add is deferred too: the next convolution and the residual sum apply it (OCT_XF_AFFINE)
         i = ops.conv_bn_act(dt, a, self.init_conv, x1=a1, lazy=True)
         # relu(bn(conv0(i))) has one consumer, a convolution: it is never written (deferred activation)
@@ -223,7 +229,7 @@ class up_conv(HipModule):
         dt = self.compute_dtype
         if not self._relu or _drops(self):   # general schedule (see _check_act): a materialised tensor, also for lazy=True
             t = ops.conv_bn_act(dt, ops.BilinearUp.apply(dt, self._factor, a), self.up[1], self.up[2])
-            return self.up[4](ops.dropout2d(t, self.up[3].p, self.up[3].training))
+            return _act(self.up[4], ops.dropout2d(t, self.up[3].p, self.up[3].training))
         return ops.conv_bn_act(dt, ops.BilinearUp.apply(dt, self._factor, a), self.up[1], self.up[2], L.ACT_RELU, lazy=lazy)
 
     def forward(self, x):

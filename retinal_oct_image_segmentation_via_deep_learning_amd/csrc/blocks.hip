@@ -105,6 +105,10 @@ extern "C" int oct_act_bwd(int dtype, const void* dout, const void* out, int act
 // k x k / stride k max-pooling of a materialised activation (torch.nn.MaxPool2d(k)); backward
 // routes the gradient to the first maximum in row-major window order, like torch.
 // ---------------------------------------------------------------------------------------------
+// torch's window update rule (max_pool2d, max_pool3d): a candidate wins when it is larger or NaN, so a NaN in
+// the window is the result (the last NaN in scanning order, where the gradient also goes).  fmaxf would drop it.
+__device__ __forceinline__ bool pool_takes(float v, float m) { return v > m || __builtin_isnan(v); }
+
 template <typename T, int V>
 __global__ void maxpool_fwd_kernel(const T* __restrict__ a, T* __restrict__ out, int n, int h, int w, int c, int k) {
   const int G = c / V;
@@ -121,7 +125,7 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ a, T* __restrict__ out,
         float v[V];
         load_vec<T, V>(a + (((size_t)img * h + yo * k + dy) * w + xo * k + dx) * c + g * V, v);
 #pragma unroll
-        for (int j = 0; j < V; ++j) m[j] = fmaxf(m[j], v[j]);
+        for (int j = 0; j < V; ++j) if (pool_takes(v[j], m[j])) m[j] = v[j];
       }
     store_vec<T, V>(out + (((size_t)img * ho + yo) * wo + xo) * c + g * V, m);
   }
@@ -142,7 +146,7 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ a, const T* __restrict_
       float v[V];
       load_vec<T, V>(a + (((size_t)img * h + yo * k + q / k) * w + xo * k + q % k) * c + g * V, v);
 #pragma unroll
-      for (int j = 0; j < V; ++j) if (v[j] > m[j]) { m[j] = v[j]; arg[j] = q; }
+      for (int j = 0; j < V; ++j) if (pool_takes(v[j], m[j])) { m[j] = v[j]; arg[j] = q; }
     }
     load_vec<T, V>(dout + (((size_t)img * ho + yo) * wo + xo) * c + g * V, d);
     for (int q = 0; q < k * k; ++q) {
@@ -190,6 +194,9 @@ extern "C" int oct_maxpool_bwd(int dtype, const void* a, const void* dout, void*
 // recomputing the forward's own (i0, lambda) so both directions agree to the last bit.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void bil_src(int o, float r, int in, int& i0, int& i1, float& l1) {
+  // s is the ROUNDED fp32 product (the documented contract, and what chose i0): without this the compiler contracts
+  // lambda = r*o - i0 into one fma of the unrounded product, up to half an ulp of s away -- an error that grows with o
+#pragma clang fp contract(off)
   const float s = r * (float)o;
   i0 = (int)s;
   if (i0 > in - 1) i0 = in - 1;
@@ -535,7 +542,7 @@ __global__ void maxpool_idx_fwd_kernel(const T* __restrict__ a, T* __restrict__ 
       float v[V];
       load_vec<T, V>(a + (((size_t)img * h + iy) * w + ix) * c + g * V, v);
 #pragma unroll
-      for (int j = 0; j < V; ++j) if (v[j] > m[j]) { m[j] = v[j]; arg[j] = iy * w + ix; }
+      for (int j = 0; j < V; ++j) if (pool_takes(v[j], m[j])) { m[j] = v[j]; arg[j] = iy * w + ix; }
     }
     const size_t o = (((size_t)img * ho + yo) * wo + xo) * c + g * V;
     store_vec<T, V>(out + o, m);
@@ -615,7 +622,7 @@ __global__ void maxpool_code_fwd_kernel(const T* __restrict__ a, T* __restrict__
       float v[V];
       load_vec<T, V>(a + (((size_t)img * h + iy) * w + ix) * c + g * V, v);
 #pragma unroll
-      for (int j = 0; j < V; ++j) if (v[j] > m[j]) { m[j] = v[j]; arg[j] = (unsigned char)q; }
+      for (int j = 0; j < V; ++j) if (pool_takes(v[j], m[j])) { m[j] = v[j]; arg[j] = (unsigned char)q; }
     }
     const size_t o = (((size_t)img * ho + yo) * wo + xo) * c + g * V;
     store_vec<T, V>(out + o, m);
@@ -698,7 +705,7 @@ extern "C" int oct_window_gather(int dtype, const void* x, const unsigned char* 
 // ---------------------------------------------------------------------------------------------
 // MaxPool3d(2) = 2x2 pooling inside every slice (oct_bn_relu_pool_fwd) followed by THIS pairwise maximum over
 // consecutive slices; the first maximum in torch's (d, h, w) scanning order is "slice 0 unless slice 1 is strictly
-// larger", so the backward routing decomposes the same way: oct_depth_pool_bwd, then the 2-D routing of
+// larger (or NaN, pool_takes)", so the backward routing decomposes the same way: oct_depth_pool_bwd, then the 2-D routing of
 // oct_dact_bn_reduce.  p2: (nvol, 2*dout, m) with m = (h/2)*(w/2)*c contiguous elements per slice.
 // ---------------------------------------------------------------------------------------------
 template <typename T, int V>
@@ -710,7 +717,7 @@ __global__ void depth_pool_fwd_kernel(const T* __restrict__ p2, T* __restrict__ 
     load_vec<T, V>(p2 + ((2 * slab) * mvec + e) * V, a);
     load_vec<T, V>(p2 + ((2 * slab + 1) * mvec + e) * V, b);
 #pragma unroll
-    for (int j = 0; j < V; ++j) a[j] = fmaxf(a[j], b[j]);
+    for (int j = 0; j < V; ++j) if (pool_takes(b[j], a[j])) a[j] = b[j];
     store_vec<T, V>(out + i * V, a);
   }
 }
@@ -725,7 +732,7 @@ __global__ void depth_pool_bwd_kernel(const T* __restrict__ p2, const T* __restr
     load_vec<T, V>(p2 + ((2 * slab + 1) * mvec + e) * V, b);
     load_vec<T, V>(dout + i * V, d);
 #pragma unroll
-    for (int j = 0; j < V; ++j) { const bool second = b[j] > a[j]; d0[j] = second ? 0.f : d[j]; d1[j] = second ? d[j] : 0.f; }
+    for (int j = 0; j < V; ++j) { const bool second = pool_takes(b[j], a[j]); d0[j] = second ? 0.f : d[j]; d1[j] = second ? d[j] : 0.f; }
     store_vec<T, V>(dp2 + ((2 * slab) * mvec + e) * V, d0);
     store_vec<T, V>(dp2 + ((2 * slab + 1) * mvec + e) * V, d1);
   }
@@ -953,16 +960,16 @@ __global__ void __launch_bounds__(BK_THREADS) rowdot_bwd_weight_kernel(const T* 
       for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(g, xv[j], acc[k][j]);
     }
   }
-  if (part_b) {   // one LDS atomic per (pixel slot, k), then one row [K] per workgroup (summed in order by the caller's second pass)
-    __shared__ float sb[K];
-    if (threadIdx.x < K) sb[threadIdx.x] = 0.f;
-    __syncthreads();
-    if (gi == 0) {
+  if (part_b) {   // the same fixed tree as acc[][] below: fold a wave's pixel slots, one LDS slot per wave, waves in order
+    __shared__ float sb[BK_THREADS / 64][K];
 #pragma unroll
-      for (int k = 0; k < K; ++k) atomicAdd(&sb[k], bacc[k]);
+    for (int k = 0; k < K; ++k) {
+      float v = gi == 0 ? bacc[k] : 0.f;
+      for (int o = G; o < 64; o <<= 1) v += __shfl_xor(v, o);
+      if ((threadIdx.x & 63) == 0) sb[threadIdx.x >> 6][k] = v;
     }
     __syncthreads();
-    if (threadIdx.x < K) part_b[(size_t)blockIdx.x * K + threadIdx.x] = sb[threadIdx.x];
+    if (threadIdx.x < K) part_b[(size_t)blockIdx.x * K + threadIdx.x] = sb[0][threadIdx.x] + sb[1][threadIdx.x] + sb[2][threadIdx.x] + sb[3][threadIdx.x];
   }
   // lanes gi, gi + G, gi + 2G ... of a wave own the same channels: fold them, then the four waves through LDS
   __shared__ float red[BK_THREADS / 64][K * (K > 4 ? RD_WIDE_C : 512)];

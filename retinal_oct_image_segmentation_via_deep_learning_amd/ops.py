@@ -921,7 +921,8 @@ def dropout2d(a, p: float, training: bool):
     keep = keep.to(device=a.device, dtype=torch.float32)
     if tuple(keep.shape) != (n, c):
         raise RuntimeError(f"dropout mask must be [{n}, {c}], got {tuple(keep.shape)}")
-    return a * (keep / (1.0 - p)).to(a.dtype).view(n, 1, 1, c)
+    # the scale stays fp32 (bf16 would round 1/0.9 to 1.109375): one rounding of a * keep / (1 - p), as in the reference
+    return (a.float() * (keep / (1.0 - p)).view(n, 1, 1, c)).to(a.dtype)
 
 
 def materialise(dtype, a):

@@ -302,3 +302,106 @@ def test_f32_block_backward_through_frozen_batchnorm_matches_torch(golden_dir, n
     rg = dict(ref.named_parameters())
     for k, p in m.named_parameters():
         close(p.grad.cpu().numpy(), rg[k].grad.numpy(), k, 2e-3)
+
+
+def _ref_copy(m, ref):
+    ref.load_state_dict({k: v.detach().cpu() for k, v in m.state_dict().items()})
+    return ref.double().train()
+
+
+def _grads_close(m, ref, rel):
+    rg = dict(ref.named_parameters())
+    for k, p in m.named_parameters():
+        assert p.grad is not None, k
+        close(p.grad.cpu().numpy(), rg[k].grad.numpy(), k, rel)
+
+
+PRELU_BLOCKS = [("conv_block", lambda M: M.conv_block(3, 8, act=torch.nn.PReLU), (2, 3, 12, 20)),
+                ("up_conv", lambda M: M.up_conv(8, 4, act=torch.nn.PReLU), (2, 8, 7, 10))]
+
+
+@pytest.mark.parametrize("name,make,xshape", PRELU_BLOCKS, ids=[p[0] for p in PRELU_BLOCKS])
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_general_schedule_with_prelu_matches_torch(name, make, xshape, dt):
+    """a parameterised activation on the general schedule: evaluated on the fp32 view (its weight stays fp32 and gets a
+    gradient), against oracle/torch_blocks.py in float64"""
+    from oracle import torch_blocks as TB
+    torch.manual_seed(5)
+    m = make(Dropins)
+    with torch.no_grad():
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.PReLU):
+                mod.weight.fill_(float(torch.empty(()).uniform_(0.1, 0.4)))
+    ref = _ref_copy(m, make(TB))
+    m.set_compute_dtype(dt).cuda().train()
+    x = torch.randn(*xshape)
+    xd, xr = x.cuda().requires_grad_(True), x.double().requires_grad_(True)
+    out, rout = m(xd), ref(xr)
+    r = torch.randn(rout.shape)
+    (out.float() * r.cuda()).sum().backward()
+    (rout * r.double()).sum().backward()
+    o, ro = out.detach().float().cpu().numpy(), rout.detach().numpy()
+    if dt == "f32":
+        close(o, ro, "out", 1e-5, 1.0)
+        close(xd.grad.cpu().numpy(), xr.grad.numpy(), "gx", 1e-5)
+        _grads_close(m, ref, 1e-5)
+    else:   # the bf16 block test's bounds (test_bf16_block_is_close)
+        err = np.abs(o - ro)
+        assert err.max() < 0.06 * max(1.0, np.abs(ro).max()) and err.mean() < 0.01 * max(1.0, np.abs(ro).mean())
+        rg = dict(ref.named_parameters())
+        for k, p in m.named_parameters():
+            a, b = p.grad.flatten().double().cpu(), rg[k].grad.flatten()
+            assert torch.isfinite(a).all(), k
+            if float(b.norm()) > 1e-6:
+                assert float(a @ b / (a.norm() * b.norm() + 1e-30)) > 0.9, k
+    assert all(p.grad is not None for k, p in m.named_parameters() if k.endswith("weight") and p.dim() == 1 and p.numel() == 1)
+
+
+def test_f32_u_net_general_schedule_with_dropout_matches_torch():
+    """U_Net(act_func=nn.LeakyReLU, drop_rate=0.1) -- every block on the general schedule -- against oracle/torch_blocks.py
+    in float64 under the same Dropout2d keep masks: logits and every gradient.  BatchNorm runs on (random) running
+    statistics: with batch statistics this 5-level network's gradients are ill-conditioned (stock torch in fp32 is
+    percents away from float64 there), and the blocks' batch-statistics path is pinned by the block tests."""
+    from oracle import torch_blocks as TB
+    from retinal_oct_image_segmentation_via_deep_learning_amd import ops
+    from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Layers_Segment.SD_Layer_Net import unet as UN
+    kw = dict(act_func=torch.nn.LeakyReLU, drop_rate=0.1)     # the decoder's concatenations fix the widths at 64 .. 1024
+    torch.manual_seed(8)
+    m = UN.U_Net(1, 3, compute_dtype="f32", **kw)
+    g = torch.Generator().manual_seed(9)
+    with torch.no_grad():
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.BatchNorm2d):
+                mod.running_mean.copy_(0.3 * torch.randn(mod.running_mean.shape, generator=g))
+                mod.running_var.copy_(0.5 + torch.rand(mod.running_var.shape, generator=g))
+    ref = _ref_copy(m, TB.U_Net(1, 3, **kw))
+    m.cuda().train()
+    for net in (m, ref):
+        for mod in net.modules():
+            if isinstance(mod, torch.nn.BatchNorm2d):
+                mod.eval()
+    masks = []
+
+    def record(n, c, p):
+        k = (torch.rand(n, c, generator=g) >= p).float()
+        masks.append(k)
+        return k
+    x = torch.randn(2, 1, 32, 32, generator=g)
+    t = torch.randint(0, 3, (2, 32, 32), generator=g)
+    keep = ops.DROPOUT_MASK_HOOK[0]
+    try:
+        ops.DROPOUT_MASK_HOOK[0] = record
+        out = m(x.cuda())
+    finally:
+        ops.DROPOUT_MASK_HOOK[0] = keep
+    assert len(masks) == 2 * 9 + 4                 # two per conv_block, one per up_conv
+    TB.set_dropout_masks([k.double() for k in masks])
+    try:
+        rout = ref(x.double())
+        assert TB._mask_at[0] == len(masks)
+    finally:
+        TB.set_dropout_masks(None)
+    close(out.detach().cpu().numpy(), rout.detach().numpy(), "logits", 1e-5, 1.0)
+    F.cross_entropy(out, t.cuda()).backward()
+    F.cross_entropy(rout, t).backward()
+    _grads_close(m, ref, 1e-5)

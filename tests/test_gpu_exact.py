@@ -137,6 +137,33 @@ def test_fprop_bit_exact(env, shape, xform):
     np.testing.assert_allclose(s[1], s2, rtol=2e-5)            # squares are summed in fp32: not exact by construction
 
 
+NOSTATS = [s for s in PIPELINED if s[5] in (64, 128)] + [(1, 16, 32, 32, 32, 32)]
+
+
+@pytest.mark.parametrize("shape", NOSTATS)
+@pytest.mark.parametrize("xform", [False, True])
+def test_fprop_without_stats_bit_exact(env, shape, xform):
+    """the forward without BatchNorm statistics (eval mode, consumers that need none): the same exact sum, and the same
+    bits as the launch with statistics"""
+    L, E = env
+    n, h, w, c0, c1, cout = shape
+    rng = np.random.default_rng(abs(hash((shape, xform))) % 2**32 + 5)
+    eng = E.UNetEngine(1, 2, 4, "bf16")
+    src, eff = exact_src(E, rng, n, h, w, c0, c1, xform)
+    wt = pow2_weights(rng, (cout, c0 + c1, 3, 3), density=0.6 if c0 + c1 <= 128 else 0.25)
+    wp = eng._pack("w", fdev(wt), L.PACK_CONV_FPROP, cout, c0 + c1)
+    y = torch.full((n, h, w, cout), float("nan"), dtype=torch.bfloat16, device="cuda")
+    eng._conv(src, wp, cout, 9, n, h, w, y, stats=None)
+    ys = torch.full((n, h, w, cout), float("nan"), dtype=torch.bfloat16, device="cuda")
+    part = torch.full((eng._stat_blocks(cout, n, h, w, src), 2, cout), float("nan"), dtype=torch.float32, device="cuda")
+    eng._conv(src, wp, cout, 9, n, h, w, ys, stats=part)
+    torch.cuda.synchronize()
+    ref = O.conv3x3_fwd(eff, wt.astype(np.float64))
+    assert np.abs(ref).max() * 8 < 2 ** 22
+    same(host(y), to_bf16(ref), "fprop without statistics (bf16 store of the exact sum)")
+    same(host(y), host(ys), "fprop without vs with statistics")
+
+
 @pytest.mark.parametrize("shape", PIPELINED + INTERLEAVED)
 def test_dgrad_bit_exact(env, shape):
     L, E = env

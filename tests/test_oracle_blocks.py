@@ -128,3 +128,23 @@ def test_dropin_state_dicts_and_ctor_rules(golden_dir):
 def L_error():
     from retinal_oct_image_segmentation_via_deep_learning_amd import _lib
     return _lib.OctError
+
+
+def test_dropout2d_scales_in_fp32_and_rounds_once():
+    """ops.dropout2d in bf16: round_bf16(f32(a) * keep / (1 - p)); a bf16 scale (1.109375 for p = 0.1) is 0.16 % low"""
+    from retinal_oct_image_segmentation_via_deep_learning_amd import ops
+    g = torch.Generator().manual_seed(2)
+    a = torch.randn(2, 7, 11, 24, generator=g).to(torch.bfloat16)
+    keep = (torch.rand(2, 24, generator=g) > 0.3).float()
+    hook = ops.DROPOUT_MASK_HOOK[0]
+    try:
+        ops.DROPOUT_MASK_HOOK[0] = lambda n, c, p: keep
+        got = ops.dropout2d(a, 0.1, True)
+    finally:
+        ops.DROPOUT_MASK_HOOK[0] = hook
+    want = (a.float() * (keep / np.float32(0.9)).view(2, 1, 1, 24)).to(torch.bfloat16)
+    assert got.dtype == torch.bfloat16 and torch.equal(got, want)
+    exact = a.double() * (keep.double() / 0.9).view(2, 1, 1, 24)
+    assert (got.double() - exact).abs().max() <= exact.abs().max() * 2.0 ** -8
+    bf16_scale = a * (keep / 0.9).to(torch.bfloat16).view(2, 1, 1, 24)
+    assert not torch.equal(bf16_scale, want)       # the data tells the two apart
