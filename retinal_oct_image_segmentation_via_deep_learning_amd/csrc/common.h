@@ -21,20 +21,50 @@ void oct_set_error(const char* fmt, ...);
     }                                   \
   } while (0)
 int oct_check_launch(const char* what);
-// igemm2.hip: pipelined bf16 path for regular shapes (returns 1 taken / 0 not eligible / <0 error)
-int oct_conv_forward_v2(const OctConvDesc* d, const OctConvArgs* a, void* stream);
-int oct_conv_v2_stat_rows(const OctConvDesc* d);
-// gemm1.hip: transposed-convolution forward / data gradient as an eight-wave GEMM (1 taken / 0 not eligible / <0 error)
-int oct_conv_forward_g1(const OctConvDesc* d, const OctConvArgs* a, void* stream);
-int oct_conv_forward_roll3d(const OctConvDesc* d, const OctConvArgs* a, void* stream);   // roll3d.hip: 1 taken, 0 not eligible, < 0 error
-int oct_conv_roll3d_stat_rows(const OctConvDesc* d);                                        // BatchNorm partial rows it writes, or -1
-// igemm.hip: (kh, kw) of a descriptor (0, 0 -> from taps); false for unsupported sizes
-bool oct_conv_kernel_size(int taps, int kh_in, int kw_in, int* kh, int* kw);
-int oct_conv_wgrad_v2(const OctWgradDesc* d, const OctWgradArgs* a, void* stream, int* query = nullptr);
-// first.hip: direct kernels for Conv2d(1 -> F)
-int oct_first_stat_rows(const OctConvDesc* d);
-int oct_first_fprop(const OctConvDesc* d, const OctConvArgs* a, void* stream);
-int oct_first_wgrad(const OctWgradDesc* d, const OctWgradArgs* a, void* stream, int* query = nullptr);
+// more than 64 KB of dynamic LDS: opt the kernel in, once per (device, kernel); OCT_OK, or OCT_E_LAUNCH with the error set
+int oct_lds_optin(const void* kernel, int bytes);
+
+// ---- convolution dispatch ----------------------------------------------------------------------------------------------
+// conv_dispatch.hip plans each descriptor once -- the kernel instantiation and its grid -- and the launch and the size queries
+// (oct_conv_stat_blocks, oct_conv_wgrad_partials, ...) answer from that one plan.  Each kernel file keeps its eligibility and
+// geometry (*_plan: false = not this path) and its launcher.
+enum ConvPath { CONV_FIRST, CONV_ROLL3D, CONV_GEMM1, CONV_IGEMM2, CONV_IGEMM };
+struct ConvPlan {
+  ConvPath path;
+  int kernel;      // instantiation family within the path (codes in its file)
+  int grid;        // workgroups along x
+  int stat_rows;   // BatchNorm partial rows [2][cout] the launch writes (oct_conv_stat_blocks)
+  int th, nt, nblk, nitems, per_wg, interleave;   // tile rows, channels per item, persistent walk
+  bool wres;       // igemm2: register-resident weights
+};
+bool first_plan(const OctConvDesc* d, ConvPlan* pl);     // first.hip: Conv2d / Conv3d (1 -> F)
+bool roll3d_plan(const OctConvDesc* d, ConvPlan* pl);    // roll3d.hip: first-level 3x3x3 convolutions
+bool igemm2_plan(const OctConvDesc* d, ConvPlan* pl);    // igemm2.hip: pipelined bf16 kernels
+bool gemm1_plan(const OctConvDesc* d, ConvPlan* pl);     // gemm1.hip: on top of an igemm2 plan, transposed convolutions
+void igemm_plan(const OctConvDesc* d, ConvPlan* pl);     // igemm.hip: generic, everything
+int launch_first(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s);
+int launch_roll3d(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s);
+int launch_igemm2(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s);
+int launch_gemm1(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s);
+int launch_igemm(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s);
+
+enum WgradPath { WGRAD_FIRST, WGRAD_W2, WGRAD_GENERIC };
+struct WgradPlan {
+  WgradPath path;
+  int kernel;            // first layer: instantiation family (first.hip)
+  int cb, ib, th;        // wgrad2: 32-channel blocks of Cout / Cin per workgroup, tile rows
+  int grid;              // first layer, generic: workgroups along x
+  int slabs;             // partial slabs the launch writes in partials mode (oct_conv_wgrad_partials)
+  bool all_depth_taps;   // first layer: in_img_shift = OCT_IMG_SHIFT_ALL available (oct_conv_wgrad_all_depth_taps_ok)
+};
+// dbias / dy_coef: whether the launch has a bias gradient / the fused BatchNorm-backward apply (the first-layer kernels
+// take no bias gradient; the 7x3 one no fused apply)
+bool first_wgrad_plan(const OctWgradDesc* d, bool dbias, bool dy_coef, WgradPlan* pl);   // first.hip
+bool wgrad2_plan(const OctWgradDesc* d, WgradPlan* pl);                                  // wgrad2.hip
+void wgrad_plan(const OctWgradDesc* d, WgradPlan* pl);                                   // wgrad.hip: generic
+int launch_first_wgrad(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s);
+int launch_wgrad2(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s);
+int launch_wgrad(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s);
 
 // lower clamp of the on-load transform a = max(x*scale + shift, floor): 0 for BN + ReLU (OCT_XF_AFFINE_RELU), -inf for the
 // plain per-channel affine (OCT_XF_AFFINE: a deferred bias add) -- the same v_max either way

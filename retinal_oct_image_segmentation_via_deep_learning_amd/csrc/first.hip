@@ -6,7 +6,6 @@
 // Both keep the loads of the next pixel in flight while the current one is processed.
 // bf16 only; other dtypes / channel counts use the generic implicit-GEMM kernels.
 #include "common.h"
-#include <stdlib.h>
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -586,130 +585,96 @@ __global__ void __launch_bounds__(256) first_wgrad_mfma_kernel(const bf16_t* __r
   }
 }
 
-static bool f1_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("OCT_DISABLE_V2"); on = (e && e[0] == '1') ? 0 : 1; }
-  return on == 1;
-}
+// ---- host side: plans and launchers (selection order in conv_dispatch.hip) --------------------------------------------
+// kernel codes of ConvPlan / WgradPlan on this path: the matrix-pipe kernels (W % 32 == 0, F >= 32), else the VALU stencils
+enum { F1_MFMA, F1_3D, F1_DIRECT };
 static bool first_ok(int dtype, int c0, int c1, int cout, int taps) {
-  return f1_enabled() && dtype == OCT_DT_BF16 && c0 == 1 && c1 == 0 && taps == 9 && (cout == 16 || cout == 32 || cout == 64);
-}
-static bool first_mfma_enabled() {
-  static int use_mfma = -1;
-  if (use_mfma < 0) { const char* e = getenv("OCT_FIRST_MFMA"); use_mfma = (e && e[0] == '0') ? 0 : 1; }
-  return use_mfma == 1;
+  return dtype == OCT_DT_BF16 && c0 == 1 && c1 == 0 && taps == 9 && (cout == 16 || cout == 32 || cout == 64);
 }
 // ReLayNet's first layer, Conv2d(1 -> F, 7x3): the matrix-pipe kernels only (W % 32 == 0, F = 32 or 64)
 static bool first73_ok(int dtype, int c0, int c1, int cout, int taps, int kh, int kw, int w, int depth, size_t npix) {
-  return f1_enabled() && first_mfma_enabled() && dtype == OCT_DT_BF16 && c0 == 1 && c1 == 0 && taps == 21 && kh == 7 && kw == 3 &&
-         (cout == 32 || cout == 64) && (w % 32) == 0 && depth == 0 && npix < (1ull << 31);
-}
-static int first_grid(const OctConvDesc* d) {
-  const size_t work = (size_t)d->n * d->h * d->w * (d->cout / 8);   // a thread per (pixel, 8-channel group)
-  size_t b = (work + 255) / 256;
-  if (b > 4096) b = 4096;
-  return (int)b;
+  return dtype == OCT_DT_BF16 && c0 == 1 && c1 == 0 && taps == 21 && kh == 7 && kw == 3 && (cout == 32 || cout == 64) &&
+         (w % 32) == 0 && depth == 0 && npix < (1ull << 31);
 }
 
-int oct_first_stat_rows(const OctConvDesc* d) {
-  const bool k73 = first73_ok(d->dtype, d->c0, d->c1, d->cout, d->taps, d->kh, d->kw, d->w, d->depth, (size_t)d->n * d->h * d->w);
-  if (d->kh == 7 && !k73) return -1;
-  if ((!k73 && !first_ok(d->dtype, d->c0, d->c1, d->cout, d->taps)) || d->in_mode || d->out_mode || d->xform0 || d->split) return -1;
-  return first_grid(d);
+bool first_plan(const OctConvDesc* d, ConvPlan* pl) {
+  const size_t npix = (size_t)d->n * d->h * d->w;
+  const bool k73 = first73_ok(d->dtype, d->c0, d->c1, d->cout, d->taps, d->kh, d->kw, d->w, d->depth, npix);
+  if (d->kh == 7 && !k73) return false;
+  if ((!k73 && !first_ok(d->dtype, d->c0, d->c1, d->cout, d->taps)) || d->in_mode || d->out_mode || d->xform0 || d->split) return false;
+  const size_t work = npix * (d->cout / 8);   // a thread per (pixel, 8-channel group)
+  pl->path = CONV_FIRST;
+  pl->grid = pl->stat_rows = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
+  pl->kernel = ((d->w % 32) == 0 && d->cout >= 32 && npix < (1ull << 31)) ? F1_MFMA : d->depth > 0 ? F1_3D : F1_DIRECT;
+  return true;
 }
 
-int oct_first_fprop(const OctConvDesc* d, const OctConvArgs* a, void* stream) {
-  if (oct_first_stat_rows(d) < 0) return 0;
-  const int grid = first_grid(d);
-  hipStream_t s = as_stream(stream);
+int launch_first(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s) {
   float* st = d->want_stats ? a->stat_partials : nullptr;
-  static int use_mfma = -1;
-  if (use_mfma < 0) { const char* e = getenv("OCT_FIRST_MFMA"); use_mfma = (e && e[0] == '0') ? 0 : 1; }
-  if (use_mfma && (d->w % 32) == 0 && d->cout >= 32 && (size_t)d->n * d->h * d->w < (1ull << 31)) {
+  if (pl.kernel == F1_MFMA) {
     // matrix-pipe kernel: a wave per 32 consecutive pixels of a row
-#define LAUNCHM(F, KD) hipLaunchKernelGGL((first_fprop_mfma_kernel<F, KD>), dim3(grid), dim3(256), 0, s, (const bf16_t*)a->x0, \
+#define LAUNCHM(F, KD) hipLaunchKernelGGL((first_fprop_mfma_kernel<F, KD>), dim3(pl.grid), dim3(256), 0, s, (const bf16_t*)a->x0, \
                                           (const bf16_t*)a->wpacked, (bf16_t*)a->y0, st, d->n, d->h, d->w, d->depth)
     if (d->kh == 7) { if (d->cout == 32) LAUNCHM(32, 7); else LAUNCHM(64, 7); }
     else if (d->depth > 0) { if (d->cout == 32) LAUNCHM(32, 3); else LAUNCHM(64, 3); }
     else { if (d->cout == 32) LAUNCHM(32, 1); else LAUNCHM(64, 1); }
 #undef LAUNCHM
-    int rcm = oct_check_launch("first_fprop_mfma");
-    return rcm ? rcm : 1;
+    return oct_check_launch("first_fprop_mfma");
   }
-  if (d->depth > 0) {
-    if ((size_t)d->n * d->h * d->w >= (1ull << 32)) return 0;   // 32-bit voxel arithmetic
-#define LAUNCH3(F) hipLaunchKernelGGL(first_fprop3d_kernel<F>, dim3(grid), dim3(256), 0, s, (const bf16_t*)a->x0, \
+  if (pl.kernel == F1_3D) {
+#define LAUNCH3(F) hipLaunchKernelGGL(first_fprop3d_kernel<F>, dim3(pl.grid), dim3(256), 0, s, (const bf16_t*)a->x0, \
                                       (const bf16_t*)a->wpacked, (bf16_t*)a->y0, st, d->n, d->h, d->w, d->depth)
     if (d->cout == 16) LAUNCH3(16); else if (d->cout == 32) LAUNCH3(32); else LAUNCH3(64);
 #undef LAUNCH3
-    int rc3 = oct_check_launch("first_fprop3d");
-    return rc3 ? rc3 : 1;
+    return oct_check_launch("first_fprop3d");
   }
-#define LAUNCH(F) hipLaunchKernelGGL(first_fprop_kernel<F>, dim3(grid), dim3(256), 0, s, (const bf16_t*)a->x0, \
+#define LAUNCH(F) hipLaunchKernelGGL(first_fprop_kernel<F>, dim3(pl.grid), dim3(256), 0, s, (const bf16_t*)a->x0, \
                                      (const bf16_t*)a->wpacked,                                      (bf16_t*)a->y0, st, d->n, d->h, d->w)
   if (d->cout == 16) LAUNCH(16); else if (d->cout == 32) LAUNCH(32); else LAUNCH(64);
 #undef LAUNCH
-  int rc = oct_check_launch("first_fprop");
-  return rc ? rc : 1;
+  return oct_check_launch("first_fprop");
 }
 
-// Host query behind OctWgradArgs.dy_coef: whether oct_conv_wgrad can apply the BatchNorm backward on load
-// for this descriptor (today: the direct first-layer kernel; OCT_DISABLE_V2=1 switches it off with the
-// other pipelined kernels, and the caller then materialises dY with oct_bn_bwd_apply).
-extern "C" int oct_conv_wgrad_fused_apply_ok(const OctWgradDesc* d) {
-  if (!d) return 0;
-  if (!first_ok(d->dtype, d->c0, d->c1, d->cout, d->taps) || d->xform0 || d->dy_mode) return 0;
-  return (size_t)d->n * d->h * d->w < (1u << 31) ? 1 : 0;
-}
-
-// Host query: 1 when oct_conv_wgrad accepts in_img_shift = OCT_IMG_SHIFT_ALL for this descriptor (all three depth taps of a
-// Conv3d(1 -> F) weight gradient in one launch, dwp = [3][9][cout]); else the caller launches once per depth tap.
-extern "C" int oct_conv_wgrad_all_depth_taps_ok(const OctWgradDesc* d) {
-  if (!d || d->depth <= 0 || d->partials) return 0;
-  if (!first_ok(d->dtype, d->c0, d->c1, d->cout, d->taps) || d->xform0 || d->dy_mode) return 0;
-  const char* e = getenv("OCT_FIRST_MFMA");
-  if (e && e[0] == '0') return 0;
-  return ((d->w % 32) == 0 && d->cout >= 32 && (size_t)d->n * d->h * d->w < (1u << 31)) ? 1 : 0;
-}
-
-int oct_first_wgrad(const OctWgradDesc* d, const OctWgradArgs* a, void* stream, int* query) {
-  const bool k73 = first73_ok(d->dtype, d->c0, d->c1, d->cout, d->taps, d->kh, d->kw, d->w, d->depth, (size_t)d->n * d->h * d->w);
-  if (d->kh == 7 && (!k73 || (!query && a->dy_coef))) return 0;
-  if ((!k73 && !first_ok(d->dtype, d->c0, d->c1, d->cout, d->taps)) || d->xform0 || d->dy_mode) return 0;
-  if (!query && a->dbias) return 0;   // no bias-gradient path in the direct kernel: the MFMA kernels take it
-  if (!query && a->dy_coef && (!a->dy_y || !a->dy_scale || !a->dy_shift)) { oct_set_error("oct_conv_wgrad: fused apply needs y, scale, shift"); return OCT_E_INVALID; }
-  const size_t total = (size_t)d->n * d->h * d->w * (d->cout / 8);
-  if ((size_t)d->n * d->h * d->w >= (1u << 31)) return 0;   // 32-bit pixel arithmetic in the kernel
-  size_t b = (total + 255) / 256;
-  if (b > 512) b = 512;   // two workgroups per CU: 0.54 ms against 0.62 at 4096 (fprop, write-dominated, prefers 2048-4096)
-  if (query) { *query = (int)b; return 1; }
-  const int part_mode = d->partials ? 1 : 0;
-  hipStream_t s = as_stream(stream);
-  static int use_mfma = -1;
-  if (use_mfma < 0) { const char* e = getenv("OCT_FIRST_MFMA"); use_mfma = (e && e[0] == '0') ? 0 : 1; }
+// dbias: no bias-gradient path in these kernels; dy_coef (the fused BatchNorm-backward apply): not on the 7x3 kernel
+bool first_wgrad_plan(const OctWgradDesc* d, bool dbias, bool dy_coef, WgradPlan* pl) {
+  const size_t npix = (size_t)d->n * d->h * d->w;
+  const bool k73 = first73_ok(d->dtype, d->c0, d->c1, d->cout, d->taps, d->kh, d->kw, d->w, d->depth, npix);
+  if (d->kh == 7 && (!k73 || dy_coef)) return false;
+  if ((!k73 && !first_ok(d->dtype, d->c0, d->c1, d->cout, d->taps)) || d->xform0 || d->dy_mode || dbias) return false;
+  if (npix >= (1u << 31)) return false;   // 32-bit pixel arithmetic in the kernel
+  const size_t total = npix * (d->cout / 8);
+  const bool mfma_ok = (d->w % 32) == 0 && d->cout >= 32;
+  pl->path = WGRAD_FIRST;
+  // two workgroups per CU: 0.54 ms against 0.62 at 4096 (fprop, write-dominated, prefers 2048-4096)
+  pl->grid = pl->slabs = (int)((total + 255) / 256 < 512 ? (total + 255) / 256 : 512);
+  // all depth taps at once: the matrix-pipe kernel only
+  pl->all_depth_taps = d->depth > 0 && !d->partials && mfma_ok;
   const bool all_taps = d->depth > 0 && d->in_img_shift == OCT_IMG_SHIFT_ALL;
-  if (use_mfma && (d->depth == 0 || all_taps) && (d->w % 32) == 0 && d->cout >= 32) {
-#define LAUNCHM(F, KD) hipLaunchKernelGGL((first_wgrad_mfma_kernel<F, KD>), dim3((int)b), dim3(256), 0, s, (const bf16_t*)a->x0, \
+  pl->kernel = (d->depth == 0 || all_taps) && mfma_ok ? F1_MFMA : d->depth > 0 ? F1_3D : F1_DIRECT;
+  return true;
+}
+
+int launch_first_wgrad(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s) {
+  const int part_mode = d->partials ? 1 : 0;
+  if (pl.kernel == F1_MFMA) {
+#define LAUNCHM(F, KD) hipLaunchKernelGGL((first_wgrad_mfma_kernel<F, KD>), dim3(pl.grid), dim3(256), 0, s, (const bf16_t*)a->x0, \
                                           (const bf16_t*)a->dy, a->dwp, d->n, d->h, d->w, \
                                           (const bf16_t*)a->dy_y, a->dy_coef, a->dy_scale, a->dy_shift, part_mode, d->depth)
-    if (k73) { if (d->cout == 32) LAUNCHM(32, 7); else LAUNCHM(64, 7); }
-    else if (all_taps) { if (d->cout == 32) LAUNCHM(32, 3); else LAUNCHM(64, 3); }
+    if (d->kh == 7) { if (d->cout == 32) LAUNCHM(32, 7); else LAUNCHM(64, 7); }
+    else if (d->depth > 0) { if (d->cout == 32) LAUNCHM(32, 3); else LAUNCHM(64, 3); }
     else { if (d->cout == 32) LAUNCHM(32, 1); else LAUNCHM(64, 1); }
 #undef LAUNCHM
-    int rcm = oct_check_launch("first_wgrad_mfma");
-    return rcm ? rcm : 1;
+    return oct_check_launch("first_wgrad_mfma");
   }
-  if (all_taps) return 0;   // only the matrix-pipe kernel takes all depth taps at once (oct_conv_wgrad_all_depth_taps_ok)
-#define LAUNCH(F) hipLaunchKernelGGL(first_wgrad_kernel<F>, dim3((int)b), dim3(256), 0, s, (const bf16_t*)a->x0, \
+#define LAUNCH(F) hipLaunchKernelGGL(first_wgrad_kernel<F>, dim3(pl.grid), dim3(256), 0, s, (const bf16_t*)a->x0, \
                                      (const bf16_t*)a->dy, a->dwp, d->n, d->h, d->w, \
                                      (const bf16_t*)a->dy_y, a->dy_coef, a->dy_scale, a->dy_shift, part_mode)
-#define LAUNCHZ(F) hipLaunchKernelGGL((first_wgrad_kernel<F, true>), dim3((int)b), dim3(256), 0, s, (const bf16_t*)a->x0, \
+#define LAUNCHZ(F) hipLaunchKernelGGL((first_wgrad_kernel<F, true>), dim3(pl.grid), dim3(256), 0, s, (const bf16_t*)a->x0, \
                                       (const bf16_t*)a->dy, a->dwp, d->n, d->h, d->w, \
                                       (const bf16_t*)a->dy_y, a->dy_coef, a->dy_scale, a->dy_shift, part_mode, d->depth, d->in_img_shift)
-  if (d->depth > 0) { if (d->cout == 16) LAUNCHZ(16); else if (d->cout == 32) LAUNCHZ(32); else LAUNCHZ(64); }
+  if (pl.kernel == F1_3D) { if (d->cout == 16) LAUNCHZ(16); else if (d->cout == 32) LAUNCHZ(32); else LAUNCHZ(64); }
   else if (d->cout == 16) LAUNCH(16); else if (d->cout == 32) LAUNCH(32); else LAUNCH(64);
 #undef LAUNCH
 #undef LAUNCHZ
-  int rc = oct_check_launch("first_wgrad");
-  return rc ? rc : 1;
+  return oct_check_launch("first_wgrad");
 }

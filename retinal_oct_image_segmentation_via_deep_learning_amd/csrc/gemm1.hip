@@ -20,7 +20,6 @@
 // Same packed weights (OCT_PACK_DECONV_FPROP / _DGRAD), same addressing modes and results as igemm2's one-tap instantiations, which
 // stay for N % 256 != 0, ragged tiles, BatchNorm sums and the volumetric modes.
 #include "common.h"
-#include <stdlib.h>
 
 struct Gemm1Params {
   const bf16_t* x; const float* sc; const float* sh; const bf16_t* wp; bf16_t* y; const float* bias;
@@ -282,50 +281,41 @@ __global__ void __launch_bounds__(512) gemm1_kernel(const Gemm1Params p) {
   }
 }
 
-static bool g1_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("OCT_GEMM1"); on = (e && e[0] == '0') ? 0 : 1; }
-  return on == 1;
-}
-
-// returns 1 when taken, 0 when the shape is not eligible (the caller falls through to igemm2's one-tap kernels)
-int oct_conv_forward_g1(const OctConvDesc* d, const OctConvArgs* a, void* stream) {
-  if (!g1_enabled() || d->taps != 1 || d->dtype != OCT_DT_BF16) return 0;
+// Planned on top of an igemm2 plan (conv_dispatch.hip): takes it over for the transposed convolutions with Cout % 256 == 0.
+// No BatchNorm sums on this path: stat_rows stays igemm2's answer.
+bool gemm1_plan(const OctConvDesc* d, ConvPlan* pl) {
+  if (d->taps != 1 || d->dtype != OCT_DT_BF16) return false;
   const bool fwd = d->in_mode == OCT_IN_PLAIN && d->out_mode == OCT_OUT_D2S;
   const bool bwd = d->in_mode == OCT_IN_S2D && d->out_mode == OCT_OUT_PLAIN;
-  if (!fwd && !bwd) return 0;
-  if (d->c1 != 0 || d->want_stats || d->split != 0 || d->depth != 0 || d->out_img_mul != 0) return 0;
-  if ((d->w % 32) != 0 || (d->h % 8) != 0 || (d->c0 % 64) != 0 || (d->cout % 256) != 0) return 0;   // 64-channel chunks
-  if (fwd && ((d->cout >> 2) % 32) != 0) return 0;
-  if (fwd && d->xform0 != OCT_XF_AFFINE_RELU && d->xform0 != OCT_XF_NONE) return 0;
-  if (bwd && d->xform0 != OCT_XF_NONE) return 0;
+  if (!fwd && !bwd) return false;
+  if (d->c1 != 0 || d->want_stats || d->split != 0 || d->depth != 0 || d->out_img_mul != 0) return false;
+  if ((d->w % 32) != 0 || (d->h % 8) != 0 || (d->c0 % 64) != 0 || (d->cout % 256) != 0) return false;   // 64-channel chunks
+  if (fwd && ((d->cout >> 2) % 32) != 0) return false;
+  if (fwd && d->xform0 != OCT_XF_AFFINE_RELU && d->xform0 != OCT_XF_NONE) return false;
+  if (bwd && d->xform0 != OCT_XF_NONE) return false;
   const int ktot = bwd ? 4 * d->c0 : d->c0;
-  if (d->c0 > 1024 || d->cout > 4096) return 0;
-  if (ktot < 256) return 0;   // K = 128 (upconv2 forward at 128 x 256): HBM-bound, 3 % slower here than on igemm2 (same box, r3)
+  if (d->c0 > 1024 || d->cout > 4096) return false;
+  if (ktot < 256) return false;   // K = 128 (upconv2 forward at 128 x 256): HBM-bound, 3 % slower here than on igemm2 (same box, r3)
+  pl->path = CONV_GEMM1;
+  pl->nblk = d->cout / 256;
+  pl->nitems = (d->w / 32) * (d->h / 8) * d->n * pl->nblk;
+  const int target = pl->nitems < 256 ? pl->nitems : 256;
+  pl->per_wg = (pl->nitems + target - 1) / target;
+  pl->grid = (pl->nitems + pl->per_wg - 1) / pl->per_wg;
+  return true;
+}
+
+int launch_gemm1(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s) {
+  const bool fwd = d->out_mode == OCT_OUT_D2S;
+  const int ktot = fwd ? d->c0 : 4 * d->c0;
   Gemm1Params p;
   p.x = (const bf16_t*)a->x0; p.sc = a->scale0; p.sh = a->shift0; p.wp = (const bf16_t*)a->wpacked;
   p.y = (bf16_t*)a->y0; p.bias = a->bias;
   p.n = d->n; p.h = d->h; p.w = d->w; p.c0 = d->c0; p.cout = d->cout; p.ktot = ktot; p.nch = ktot / 64; p.nk16 = ktot / 16;
-  p.nblk = d->cout / 256; p.tiles_x = d->w / 32; p.tiles_y = d->h / 8;
-  p.nitems = p.tiles_x * p.tiles_y * d->n * p.nblk;
-  int grid = p.nitems < 256 ? p.nitems : 256;
-  p.per_wg = (p.nitems + grid - 1) / grid;
-  grid = (p.nitems + p.per_wg - 1) / p.per_wg;
+  p.nblk = pl.nblk; p.tiles_x = d->w / 32; p.tiles_y = d->h / 8; p.nitems = pl.nitems; p.per_wg = pl.per_wg;
   const int lds = G1_NBUF * G1_BUFB + 2 * 1024 * 4 + 8 * 32 * 80 + 1024 * 4;
-  hipStream_t s = as_stream(stream);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm1_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm1_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm1_kernel<false, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
-  if (fwd) {
-    if (d->xform0 != OCT_XF_NONE) hipLaunchKernelGGL((gemm1_kernel<true, false, true>), dim3(grid), dim3(512), lds, s, p);
-    else hipLaunchKernelGGL((gemm1_kernel<false, false, true>), dim3(grid), dim3(512), lds, s, p);
-  } else {
-    hipLaunchKernelGGL((gemm1_kernel<false, true, false>), dim3(grid), dim3(512), lds, s, p);
-  }
-  int rc = oct_check_launch("gemm1");
-  return rc ? rc : 1;
+  const auto kern = !fwd ? gemm1_kernel<false, true, false> : d->xform0 != OCT_XF_NONE ? gemm1_kernel<true, false, true> : gemm1_kernel<false, false, true>;
+  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), lds)) return rc;
+  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), lds, s, p);
+  return oct_check_launch("gemm1");
 }

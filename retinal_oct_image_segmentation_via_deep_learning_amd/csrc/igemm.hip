@@ -475,90 +475,33 @@ extern "C" int oct_pack_weights_batch(int dtype, int count, const OctPackJob* jo
   return oct_check_launch("pack_weights_batch");
 }
 
-// ---- host dispatch ------------------------------------------------------------------------------
-struct TileCfg { int th; int nt; };
-static TileCfg pick_cfg(int cout) {
-  if (cout <= 32) return {8, 32};
-  if (cout <= 64) return {8, 64};
-  return {8, 128};
-}
-
-extern "C" int oct_conv_stat_blocks(const OctConvDesc* d) {
-  if (!d) return 0;
-  {
-    const int f1 = oct_first_stat_rows(d);
-    if (f1 >= 0) return f1;
-    const int v2 = oct_conv_v2_stat_rows(d);
-    if (v2 >= 0) return v2;
-  }
-  const TileCfg c = pick_cfg(d->cout);
-  return ceil_div(d->w, 32) * ceil_div(d->h, c.th) * d->n;
+// ---- generic kernel: plan and launcher (selection order in conv_dispatch.hip) -------------------------------------------
+// 8-row tiles; 32, 64 or 128 output channels per workgroup
+void igemm_plan(const OctConvDesc* d, ConvPlan* pl) {
+  pl->path = CONV_IGEMM;
+  pl->th = 8;
+  pl->nt = d->cout <= 32 ? 32 : d->cout <= 64 ? 64 : 128;
+  pl->grid = pl->stat_rows = ceil_div(d->w, 32) * ceil_div(d->h, pl->th) * d->n;
 }
 
 template <typename T, int KH, int KW, int WM, int WN, int MF, int NF>
-static void launch_igemm_cfg(const IgemmParams& p, dim3 grid, hipStream_t s) {
+static int launch_igemm_cfg(const IgemmParams& p, dim3 grid, hipStream_t s) {
   constexpr int TH = WM * MF, NT = WN * NF * 32, PIXB = 32 * (int)sizeof(T) + 16;
   constexpr int lds = (TH + KH - 1) * (32 + KW - 1) * PIXB + WM * 2 * NT * (int)sizeof(float);
-  if (lds > 64 * 1024) {   // 7x3 in fp32: 14 x 34 pixels x 144 B
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<T, KH, KW, WM, WN, MF, NF, 32>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      attr = true;
-    }
-  }
+  if (lds > 64 * 1024)   // 7x3 in fp32: 14 x 34 pixels x 144 B
+    if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&igemm_kernel<T, KH, KW, WM, WN, MF, NF, 32>), lds)) return rc;
   hipLaunchKernelGGL((igemm_kernel<T, KH, KW, WM, WN, MF, NF, 32>), grid, dim3(256), lds, s, p);
-}
-template <typename T, int KH, int KW>
-static int launch_igemm(const OctConvDesc* d, const IgemmParams& p, hipStream_t s) {
-  const TileCfg c = pick_cfg(d->cout);
-  dim3 grid(p.tiles_x * p.tiles_y * p.n, ceil_div(d->cout, c.nt));
-  if (c.nt == 32) launch_igemm_cfg<T, KH, KW, 4, 1, 2, 1>(p, grid, s);
-  else if (c.nt == 64) launch_igemm_cfg<T, KH, KW, 2, 2, 4, 1>(p, grid, s);
-  else launch_igemm_cfg<T, KH, KW, 2, 2, 4, 2>(p, grid, s);
   return oct_check_launch("igemm");
 }
-
-// kernel size of a descriptor: kh = kw = 0 means "from taps" (9 -> 3x3, 1 -> 1x1), as before the fields existed
-bool oct_conv_kernel_size(int taps, int kh_in, int kw_in, int* kh, int* kw) {
-  if (kh_in == 0 && kw_in == 0) {
-    if (taps == 9) { *kh = 3; *kw = 3; return true; }
-    if (taps == 1) { *kh = 1; *kw = 1; return true; }
-    return false;
-  }
-  *kh = kh_in; *kw = kw_in;
-  return taps == kh_in * kw_in && ((kh_in == 3 && kw_in == 3) || (kh_in == 1 && kw_in == 1) || (kh_in == 7 && kw_in == 3));
+template <typename T, int KH, int KW>
+static int launch_igemm_t(const ConvPlan& pl, const IgemmParams& p, hipStream_t s) {
+  const dim3 grid(pl.grid, ceil_div(p.cout, pl.nt));
+  if (pl.nt == 32) return launch_igemm_cfg<T, KH, KW, 4, 1, 2, 1>(p, grid, s);
+  if (pl.nt == 64) return launch_igemm_cfg<T, KH, KW, 2, 2, 4, 1>(p, grid, s);
+  return launch_igemm_cfg<T, KH, KW, 2, 2, 4, 2>(p, grid, s);
 }
 
-extern "C" int oct_conv_forward(const OctConvDesc* d, const OctConvArgs* a, void* stream) {
-  OCT_CHECK(d && a, "oct_conv_forward: null descriptor");
-  OCT_CHECK(d->dtype == OCT_DT_BF16 || d->dtype == OCT_DT_F32, "oct_conv_forward: bad dtype %d", d->dtype);
-  int kh = 0, kw = 0;
-  OCT_CHECK(oct_conv_kernel_size(d->taps, d->kh, d->kw, &kh, &kw),
-            "oct_conv_forward: kernel must be 3x3 (taps 9), 1x1 (taps 1) or 7x3 (taps 21, kh=7, kw=3); got taps=%d kh=%d kw=%d",
-            d->taps, d->kh, d->kw);
-  OCT_CHECK(kh != 7 || (d->in_mode == OCT_IN_PLAIN && d->out_mode == OCT_OUT_PLAIN), "oct_conv_forward: 7x3 runs plain -> plain");
-  OCT_CHECK(d->depth >= 0 && (d->depth == 0 || (d->n % d->depth) == 0), "oct_conv_forward: n=%d is not a whole number of depth-%d volumes", d->n, d->depth);
-  OCT_CHECK(d->depth == 0 || kh != 7, "oct_conv_forward: depth taps go with the 3x3 (3x3x3) and 1x1 (2x2x2 transposed) kernels");
-  OCT_CHECK(d->out_img_mul == 0 || d->out_mode == OCT_OUT_D2S, "oct_conv_forward: the output image map belongs to D2S");
-  OCT_CHECK(d->n > 0 && d->h > 0 && d->w > 0 && d->c0 > 0 && d->c1 >= 0 && d->cout > 0,
-            "oct_conv_forward: bad shape n=%d h=%d w=%d c0=%d c1=%d cout=%d", d->n, d->h, d->w, d->c0, d->c1, d->cout);
-  OCT_CHECK(a->x0 && a->wpacked && a->y0, "oct_conv_forward: null tensor");
-  OCT_CHECK(d->c1 == 0 || a->x1, "oct_conv_forward: c1 > 0 but x1 is null");
-  OCT_CHECK(!(d->in_mode == OCT_IN_S2D && d->c1 != 0), "oct_conv_forward: S2D input takes one source");
-  OCT_CHECK(!(d->out_mode == OCT_OUT_D2S && (d->cout & 3)), "oct_conv_forward: D2S needs cout %% 4 == 0");
-  OCT_CHECK(d->split >= 0 && d->split < d->cout, "oct_conv_forward: bad split %d", d->split);
-  OCT_CHECK(d->split == 0 || a->y1, "oct_conv_forward: split without y1");
-  OCT_CHECK(d->xform0 >= 0 && d->xform0 <= OCT_XF_AFFINE && d->xform1 >= 0 && d->xform1 <= OCT_XF_AFFINE, "oct_conv_forward: bad xform");
-  OCT_CHECK(!(d->xform0 && (!a->scale0 || !a->shift0)), "oct_conv_forward: xform0 without scale/shift");
-  OCT_CHECK(!(d->xform1 && (!a->scale1 || !a->shift1)), "oct_conv_forward: xform1 without scale/shift");
-  OCT_CHECK(!(d->want_stats && !a->stat_partials), "oct_conv_forward: want_stats without buffer");
-  OCT_CHECK((size_t)d->n * d->h * d->w < (1u << 31), "oct_conv_forward: too many pixels");
-  {
-    int took = oct_first_fprop(d, a, stream);
-    if (took == 0) took = oct_conv_forward_v2(d, a, stream);
-    if (took != 0) return took < 0 ? took : OCT_OK;
-  }
+int launch_igemm(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s) {
   IgemmParams p;
   p.x0 = a->x0; p.x1 = a->x1; p.sc0 = a->scale0; p.sh0 = a->shift0; p.sc1 = a->scale1; p.sh1 = a->shift1;
   p.wp = a->wpacked; p.bias = a->bias; p.y0 = a->y0; p.y1 = a->y1;
@@ -569,10 +512,8 @@ extern "C" int oct_conv_forward(const OctConvDesc* d, const OctConvArgs* a, void
   p.nk16 = ceil_div(p.ktot, 16);
   p.cout = d->cout; p.nb32 = ceil_div(d->cout, 32);
   p.xf0 = d->xform0; p.xf1 = d->xform1; p.in_mode = d->in_mode; p.out_mode = d->out_mode; p.split = d->split;
-  const TileCfg c = pick_cfg(d->cout);
-  p.tiles_x = ceil_div(d->w, 32); p.tiles_y = ceil_div(d->h, c.th);
-  hipStream_t s = as_stream(stream);
+  p.tiles_x = ceil_div(d->w, 32); p.tiles_y = ceil_div(d->h, pl.th);
   if (d->dtype == OCT_DT_BF16)
-    return kh == 7 ? launch_igemm<bf16_t, 7, 3>(d, p, s) : kh == 3 ? launch_igemm<bf16_t, 3, 3>(d, p, s) : launch_igemm<bf16_t, 1, 1>(d, p, s);
-  return kh == 7 ? launch_igemm<float, 7, 3>(d, p, s) : kh == 3 ? launch_igemm<float, 3, 3>(d, p, s) : launch_igemm<float, 1, 1>(d, p, s);
+    return d->taps == 21 ? launch_igemm_t<bf16_t, 7, 3>(pl, p, s) : d->taps == 9 ? launch_igemm_t<bf16_t, 3, 3>(pl, p, s) : launch_igemm_t<bf16_t, 1, 1>(pl, p, s);
+  return d->taps == 21 ? launch_igemm_t<float, 7, 3>(pl, p, s) : d->taps == 9 ? launch_igemm_t<float, 3, 3>(pl, p, s) : launch_igemm_t<float, 1, 1>(pl, p, s);
 }

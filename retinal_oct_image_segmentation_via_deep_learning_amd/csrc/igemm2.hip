@@ -1325,53 +1325,47 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-struct V2Plan { bool ok; int nt; int th; bool wres; int grid; int per_wg; int nitems; int nblk; int stat_rows; int interleave; };
+// kernel codes of ConvPlan on this path
+enum { IG2_TILE, IG2_1X1, IG2_WLDS, IG2_DMA };
 
-static bool v2_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("OCT_DISABLE_V2"); on = (e && e[0] == '1') ? 0 : 1; }
-  return on == 1;
-}
-
-static V2Plan plan_v2(const OctConvDesc* d) {
-  V2Plan pl = {};
-  if (!v2_enabled()) return pl;
+bool igemm2_plan(const OctConvDesc* d, ConvPlan* out) {
   if (d->kh == 7) {
     // 7x3 (ReLayNet): the 64- and 128-channel tilings with three halo rows above and below an 8-row tile.  A last tile row of
     // one or two image rows would put padding into the bottom halo of the tile row ABOVE it, which the border codes do not
     // express (they flag rows against the last tile row only): such heights stay on the generic kernel.
     const int rem = d->h % 8;
-    if (d->taps != 21 || d->kw != 3 || d->depth > 0 || d->out_img_mul != 0 || rem == 1 || rem == 2 || (d->cout % 64) != 0) return pl;
+    if (d->taps != 21 || d->kw != 3 || d->depth > 0 || d->out_img_mul != 0 || rem == 1 || rem == 2 || (d->cout % 64) != 0) return false;
   }
-  if ((d->depth > 0 || d->out_img_mul != 0) && ((d->w % 32) != 0 || (d->h % 16) != 0)) return pl;   // volumetric: whole tiles
+  if ((d->depth > 0 || d->out_img_mul != 0) && ((d->w % 32) != 0 || (d->h % 16) != 0)) return false;   // volumetric: whole tiles
   const int cin = d->in_mode == OCT_IN_S2D ? (d->depth > 0 ? 8 : 4) * d->c0 : d->c0 + d->c1;   // channels per depth tap
   // plain 3x3: any H, W (ragged last tiles are predicated); the deconv modes need whole tiles
   const bool whole = (d->w % 32) == 0 && (d->h % 8) == 0;
   // plain -> plain (3x3, and 1x1: the attention gates' W_g / W_x, classifier heads, their data gradients): any H, W;
   // the deconv modes (1x1 with depth-to-space / space-to-depth addressing) need whole tiles
   const bool plain = d->in_mode == OCT_IN_PLAIN && d->out_mode == OCT_OUT_PLAIN;
-  pl.ok = d->dtype == OCT_DT_BF16 && (whole || plain) && (d->c0 % 32) == 0 &&
-          (d->c1 % 32) == 0 && (d->cout % 32) == 0 && (d->split % 32) == 0;
-  pl.ok = pl.ok && (d->c0 + d->c1) <= 1024 && d->cout <= 4096;   // LDS tables: 2 x 1024 BN coefficients, 1024 bias values
-  if (d->taps != 1) pl.ok = pl.ok && plain;
-  else pl.ok = pl.ok && (plain ||
-               (!d->want_stats && d->split == 0 &&
-                ((d->in_mode == OCT_IN_PLAIN && d->out_mode == OCT_OUT_D2S && ((d->cout >> 2) % 32) == 0) ||
-                 (d->in_mode == OCT_IN_S2D && d->out_mode == OCT_OUT_PLAIN && d->c1 == 0))));
-  if (!pl.ok) return pl;
+  bool ok = d->dtype == OCT_DT_BF16 && (whole || plain) && (d->c0 % 32) == 0 &&
+            (d->c1 % 32) == 0 && (d->cout % 32) == 0 && (d->split % 32) == 0;
+  ok = ok && (d->c0 + d->c1) <= 1024 && d->cout <= 4096;   // LDS tables: 2 x 1024 BN coefficients, 1024 bias values
+  if (d->taps != 1) ok = ok && plain;
+  else ok = ok && (plain ||
+            (!d->want_stats && d->split == 0 &&
+             ((d->in_mode == OCT_IN_PLAIN && d->out_mode == OCT_OUT_D2S && ((d->cout >> 2) % 32) == 0) ||
+              (d->in_mode == OCT_IN_S2D && d->out_mode == OCT_OUT_PLAIN && d->c1 == 0))));
+  if (!ok) return false;
+  ConvPlan pl = {};
+  pl.path = CONV_IGEMM2;
   pl.nt = d->cout == 32 ? 32 : (d->cout % 128 == 0 ? 128 : (d->cout % 64 == 0 ? 64 : 0));
   if (pl.nt == 128 && d->split > 0 && (d->split % 64) != 0) pl.nt = 64;   // a wave's two channel fragments leave as one 128-B line (MRG): same destination
-  if (pl.nt == 0) { pl.ok = false; return pl; }
+  if (pl.nt == 0) return false;
   pl.wres = (d->taps == 9) && (cin == 32) && (d->cout == pl.nt) && pl.nt <= 64 && d->depth == 0;   // 3-D: three chunks per item
   pl.nblk = d->cout / pl.nt;
-  // Cout = 32 (full-resolution, HBM-bound layers): 16-row tiles halve the halo overhead per output pixel
-  // 16-row tiles: Cout = 32 always; Cout = 64 with streamed weights in fprop (each wave then owns 4 rows x 64
-  // channels: half the LDS reads per MFMA, halo overhead 18/16) -- measured -2 % on fprop, neutral to worse on dgrad
-#ifndef IG2_TH16_DGRAD
-#define IG2_TH16_DGRAD 1   /* 64-channel data gradients on the 16-row two-fragment tiling too (full-line stores, MRG): 0.358 -> 0.309, 0.334 -> 0.297, 0.155 -> 0.144 ms on the three launches of cfg2 (same box) */
-#endif
-  // (the two-fragment tilings store a wave's 64 channels as one line: a concat split inside them -- split % 64 != 0 -- keeps the one-fragment tiling)
-  pl.th = (d->taps == 9 && (pl.nt == 32 || (pl.nt == 64 && (d->want_stats || IG2_TH16_DGRAD) && !pl.wres && (d->split % 64) == 0)) && (d->h % 16) == 0) ? 16 : 8;
+  // 16-row tiles halve the halo overhead per output pixel: Cout = 32 (full-resolution, HBM-bound layers) always; Cout = 64 with
+  // streamed weights, where each wave then owns 4 rows x 64 channels (half the LDS reads per MFMA, halo overhead 18/16).  Every
+  // such 64-channel 3x3 launch takes it, with or without BatchNorm sums: fprop with sums measured -2 %, the data gradients 0.358 ->
+  // 0.309, 0.334 -> 0.297, 0.155 -> 0.144 ms on the three launches of cfg2 (full-line stores, MRG, same box); the eval-mode
+  // forward (no sums) on this tiling has not been timed.  The two-fragment tilings store a wave's 64 channels as one line: a
+  // concat split inside them -- split % 64 != 0 -- keeps the one-fragment tiling.
+  pl.th = (d->taps == 9 && (pl.nt == 32 || (pl.nt == 64 && !pl.wres && (d->split % 64) == 0)) && (d->h % 16) == 0) ? 16 : 8;
   const int ntiles = ((d->w + 31) / 32) * ((d->h + pl.th - 1) / pl.th) * d->n;
   pl.nitems = ntiles * pl.nblk;
   int target = 256;  // one persistent workgroup per CU (only one fits the LDS); 512 measured 2 % slower on dgrad, 1024 4 %
@@ -1384,52 +1378,43 @@ static V2Plan plan_v2(const OctConvDesc* d) {
     pl.interleave = 1;
   }
   pl.stat_rows = pl.grid;   // one row [2][cout] per (persistent) workgroup
-  return pl;
+  // LDS-DMA staging (see the kernel): data gradients -- one source, no transform on load, whole 8-row tiles, streamed weights
+  // (7x3: the LDS-DMA variant spills 8 dwords and measured 1 % slower on ReLayNet's data gradients)
+  const bool dma = !d->xform0 && !d->xform1 && d->c1 == 0 && !d->want_stats && !pl.wres && pl.th == 8 &&
+                   d->depth == 0 && d->out_img_mul == 0 && (d->w % 32) == 0 && (d->h % 8) == 0 && pl.nt >= 64 &&
+                   ((d->taps == 9) || (d->in_mode == OCT_IN_S2D && d->out_mode == OCT_OUT_PLAIN));
+  // LDS-resident weights (see WLDS in the kernel): Cout = 32, Cin <= 64, streamed-weight 3x3 kernels on whole 16-row tiles
+  const bool wlds = d->taps == 9 && pl.nt == 32 && pl.th == 16 && !pl.wres && (d->c0 + d->c1) <= 64 && d->depth == 0 &&
+                    d->out_img_mul == 0 && (d->w % 32) == 0;
+  pl.kernel = dma ? IG2_DMA : d->taps == 1 ? IG2_1X1 : wlds ? IG2_WLDS : IG2_TILE;
+  *out = pl;
+  return true;
 }
 
-int oct_conv_v2_stat_rows(const OctConvDesc* d) {
-  const int roll = oct_conv_roll3d_stat_rows(d);   // first-level volumetric layers: the depth-rolling kernel (roll3d.hip)
-  if (roll >= 0) return roll;
-  const V2Plan pl = plan_v2(d);
-  return pl.ok ? pl.stat_rows : -1;
-}
-
+// > 64 KB of dynamic LDS: every variant opts in to the 160 KB cap
 template <int WM, int WN, int MF, int NF, bool WRES, int TAPS = 9>
-static void launch_v2(const Igemm2Params& p, int grid, hipStream_t s) {
+static int launch_v2(const Igemm2Params& p, int grid, hipStream_t s) {
   constexpr int TH = WM * MF;
   constexpr int LH = TH + (TAPS == 21 ? 6 : 2);   // halo rows: 3 + 3 for the 7x3 kernel
   const int lds = 2 * LH * 34 * ig2_pixb<TAPS, NF, WRES, false>() + (2 * WM * 2 * (WN * NF * 32) + 4 + 2 * 1024) * (int)sizeof(float) + 2 * 4 * 32 * 80 + 1024 * (int)sizeof(float) +
                   (p.stats ? 2 * p.cout * (int)sizeof(float) : 0);
-  {
-    // > 64 KB of dynamic LDS: opt in once per instantiation (all eight variants of this shape share the size class)
-    static bool attr = false;
-    if (!attr) {
-      const int cap = 160 * 1024;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, false>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-      if constexpr (!WRES && TAPS == 9) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<TAPS, WM, WN, MF, NF, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<TAPS, WM, WN, MF, NF, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-      }
-      attr = true;
-    }
-  }
   const bool ragged = (p.w % 32) != 0 || (p.h % TH) != 0;
-  if (p.depth > 0) {   // volumetric: whole tiles only (plan_v2), streamed weights
-    if constexpr (!WRES && TAPS == 9) {
-      if (p.stats) hipLaunchKernelGGL((igemm2_kernel<TAPS, WM, WN, MF, NF, false, true, false, true>), dim3(grid), dim3(512), lds, s, p);
-      else hipLaunchKernelGGL((igemm2_kernel<TAPS, WM, WN, MF, NF, false, false, false, true>), dim3(grid), dim3(512), lds, s, p);
-    }
+  void (*kern)(Igemm2Params) = nullptr;
+  if (p.depth > 0) {   // volumetric: whole tiles only (igemm2_plan), streamed weights
+    if constexpr (!WRES && TAPS == 9)
+      kern = p.stats ? igemm2_kernel<TAPS, WM, WN, MF, NF, false, true, false, true> : igemm2_kernel<TAPS, WM, WN, MF, NF, false, false, false, true>;
   } else if (ragged) {
-    if (p.stats) hipLaunchKernelGGL((igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, true, true>), dim3(grid), dim3(512), lds, s, p);
-    else hipLaunchKernelGGL((igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, false, true>), dim3(grid), dim3(512), lds, s, p);
-  } else if (p.stats) hipLaunchKernelGGL((igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, true>), dim3(grid), dim3(512), lds, s, p);
-  else hipLaunchKernelGGL((igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, false>), dim3(grid), dim3(512), lds, s, p);
+    kern = p.stats ? igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, true, true> : igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, false, true>;
+  } else {
+    kern = p.stats ? igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, true> : igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, false>;
+  }
+  if (!kern) { oct_set_error("igemm2: no depth-tap instantiation of this tiling"); return OCT_E_INVALID; }
+  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
+  return OCT_OK;
 }
 template <int WM, int WN, int MF, int NF>
-static void launch_v2_1x1(const Igemm2Params& p, int grid, hipStream_t s) {
+static int launch_v2_1x1(const Igemm2Params& p, int grid, hipStream_t s) {
   constexpr int TH = WM * MF;
   const int lds = 2 * TH * 32 * 80 + (2 * WM * 2 * (WN * NF * 32) + 4 + 2 * 1024) * (int)sizeof(float) + 2 * 4 * 32 * 80 + 1024 * (int)sizeof(float) +
                   (p.stats ? 2 * p.cout * (int)sizeof(float) : 0);
@@ -1443,62 +1428,30 @@ static void launch_v2_1x1(const Igemm2Params& p, int grid, hipStream_t s) {
     hipLaunchKernelGGL((igemm2_kernel<1, WM, WN, MF, NF, false, false, false, true>), dim3(grid), dim3(512), lds, s, p);
   else
     hipLaunchKernelGGL((igemm2_kernel<1, WM, WN, MF, NF, false, false>), dim3(grid), dim3(512), lds, s, p);
-}
-
-// LDS-resident weights (see WLDS in the kernel): Cout = 32, Cin <= 64, streamed-weight 3x3 kernels on whole tiles
-static bool wlds_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("OCT_IG2_WLDS"); on = (e && e[0] == '0') ? 0 : 1; }
-  return on == 1;
+  return OCT_OK;
 }
 template <int WM, int MF>
-static void launch_v2_wlds(const Igemm2Params& p, int grid, hipStream_t s) {
+static int launch_v2_wlds(const Igemm2Params& p, int grid, hipStream_t s) {
   constexpr int TH = WM * MF;
   const int lds = 2 * (TH + 2) * 34 * 80 + (2 * WM * 2 * 32 + 4) * (int)sizeof(float) + 2 * 64 * (int)sizeof(float) + 4 * 32 * 80 + 2 * 18 * 1024 +
                   (p.stats ? 2 * p.cout * (int)sizeof(float) : 0);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<9, WM, 1, MF, 1, false, true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<9, WM, 1, MF, 1, false, false, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  if (p.stats) hipLaunchKernelGGL((igemm2_kernel<9, WM, 1, MF, 1, false, true, false, false, false, true>), dim3(grid), dim3(512), lds, s, p);
-  else hipLaunchKernelGGL((igemm2_kernel<9, WM, 1, MF, 1, false, false, false, false, false, true>), dim3(grid), dim3(512), lds, s, p);
-}
-
-// LDS-DMA staging (see the kernel): data gradients -- one source, no transform on load, whole 8-row tiles, streamed weights
-static bool dma_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("OCT_IG2_DMA"); on = (e && e[0] == '0') ? 0 : 1; }
-  return on == 1;
+  const auto kern = p.stats ? igemm2_kernel<9, WM, 1, MF, 1, false, true, false, false, false, true> : igemm2_kernel<9, WM, 1, MF, 1, false, false, false, false, false, true>;
+  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
+  return OCT_OK;
 }
 template <int TAPS, int WM, int WN, int MF, int NF>
-static void launch_v2_dma(const Igemm2Params& p, int grid, hipStream_t s) {
+static int launch_v2_dma(const Igemm2Params& p, int grid, hipStream_t s) {
   constexpr int TH = WM * MF, HALO = TAPS != 1 ? 1 : 0, HALO_Y = TAPS == 21 ? 3 : HALO;
   constexpr int NSLOT = ((TH + 2 * HALO_Y) * (32 + 2 * HALO) + 63) / 64, NBUF = TAPS != 1 ? 3 : 6;
   constexpr int lds = NBUF * NSLOT * 4096 + (2 * WM * 2 * (WN * NF * 32) + 4 + 2 * 1024) * (int)sizeof(float) + 2 * 4 * 32 * 80 + 1024 * (int)sizeof(float);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm2_kernel<TAPS, WM, WN, MF, NF, false, false, false, false, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
+  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&igemm2_kernel<TAPS, WM, WN, MF, NF, false, false, false, false, true>), lds)) return rc;
   hipLaunchKernelGGL((igemm2_kernel<TAPS, WM, WN, MF, NF, false, false, false, false, true>), dim3(grid), dim3(512), lds, s, p);
+  return OCT_OK;
 }
 
-// returns 1 when the launch was taken by this path, 0 when the shape is not eligible, <0 on error
-int oct_conv_forward_v2(const OctConvDesc* d, const OctConvArgs* a, void* stream) {
-  if (d->depth > 0) {   // 3x3x3 with 32 input channels per depth tap: the depth-rolling walk (roll3d.hip)
-    const int rc = oct_conv_forward_roll3d(d, a, stream);
-    if (rc != 0) return rc;
-  }
-  const V2Plan pl = plan_v2(d);
-  if (!pl.ok) return 0;
-  if (d->taps == 1) {   // transposed convolutions with N % 256 == 0: the eight-wave GEMM kernel (gemm1.hip)
-    const int rc = oct_conv_forward_g1(d, a, stream);
-    if (rc != 0) return rc;
-  }
+int launch_igemm2(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s) {
   Igemm2Params p;
   p.x0 = (const bf16_t*)a->x0; p.x1 = (const bf16_t*)a->x1;
   p.sc0 = a->scale0; p.sh0 = a->shift0; p.sc1 = a->scale1; p.sh1 = a->shift1;
@@ -1518,34 +1471,27 @@ int oct_conv_forward_v2(const OctConvDesc* d, const OctConvArgs* a, void* stream
   p.nch = ktot / 32; p.nk16 = ktot / 16;
   p.depth = d->depth; p.nchc = (d->c0 + d->c1) / 32; p.oimg_mul = d->out_img_mul; p.oimg_add = d->out_img_add;
   if (p.depth > 0 && p.oimg_mul == 0) p.oimg_mul = 1;   // the D3 instantiation always applies the image map
-  hipStream_t s = as_stream(stream);
-  const bool dma = dma_enabled() && !d->xform0 && !d->xform1 && d->c1 == 0 && !d->want_stats && !pl.wres && pl.th == 8 &&
-                   d->depth == 0 && d->out_img_mul == 0 && (d->w % 32) == 0 && (d->h % 8) == 0 && pl.nt >= 64 &&
-                   ((d->taps == 9) || (d->in_mode == OCT_IN_S2D && d->out_mode == OCT_OUT_PLAIN));   // (7x3: the LDS-DMA variant spills 8 dwords and measured 1 % slower on ReLayNet's data gradients)
-  if (dma) {
-    if (d->taps == 9) { if (pl.nt == 64) launch_v2_dma<9, 2, 2, 4, 1>(p, pl.grid, s); else launch_v2_dma<9, 2, 2, 4, 2>(p, pl.grid, s); }
-    else { if (pl.nt == 64) launch_v2_dma<1, 2, 2, 4, 1>(p, pl.grid, s); else launch_v2_dma<1, 2, 2, 4, 2>(p, pl.grid, s); }
+  const int g = pl.grid;
+  int rc;
+  if (pl.kernel == IG2_DMA) {
+    if (d->taps == 9) rc = pl.nt == 64 ? launch_v2_dma<9, 2, 2, 4, 1>(p, g, s) : launch_v2_dma<9, 2, 2, 4, 2>(p, g, s);
+    else rc = pl.nt == 64 ? launch_v2_dma<1, 2, 2, 4, 1>(p, g, s) : launch_v2_dma<1, 2, 2, 4, 2>(p, g, s);
+  } else if (pl.kernel == IG2_1X1) {
+    rc = pl.nt == 32 ? launch_v2_1x1<4, 1, 2, 1>(p, g, s) : pl.nt == 64 ? launch_v2_1x1<2, 2, 4, 1>(p, g, s) : launch_v2_1x1<2, 2, 4, 2>(p, g, s);
+  } else if (pl.kernel == IG2_WLDS) {
+    rc = launch_v2_wlds<4, 4>(p, g, s);
   } else if (d->taps == 21) {
-    if (pl.nt == 64) launch_v2<2, 2, 4, 1, false, 21>(p, pl.grid, s); else launch_v2<2, 2, 4, 2, false, 21>(p, pl.grid, s);
-  } else if (d->taps == 1) {
-    if (pl.nt == 32) launch_v2_1x1<4, 1, 2, 1>(p, pl.grid, s);
-    else if (pl.nt == 64) launch_v2_1x1<2, 2, 4, 1>(p, pl.grid, s);
-    else launch_v2_1x1<2, 2, 4, 2>(p, pl.grid, s);
+    rc = pl.nt == 64 ? launch_v2<2, 2, 4, 1, false, 21>(p, g, s) : launch_v2<2, 2, 4, 2, false, 21>(p, g, s);
   } else if (pl.nt == 32 && pl.th == 16) {
-    const bool wlds = wlds_enabled() && !pl.wres && d->cout == 32 && (d->c0 + d->c1) <= 64 && d->depth == 0 && d->out_img_mul == 0 &&
-                      (d->w % 32) == 0 && (d->h % 16) == 0;
-    if (pl.wres) launch_v2<4, 1, 4, 1, true>(p, pl.grid, s);
-    else if (wlds) launch_v2_wlds<4, 4>(p, pl.grid, s);
-    else launch_v2<4, 1, 4, 1, false>(p, pl.grid, s);
+    rc = pl.wres ? launch_v2<4, 1, 4, 1, true>(p, g, s) : launch_v2<4, 1, 4, 1, false>(p, g, s);
   } else if (pl.nt == 32) {
-    if (pl.wres) launch_v2<4, 1, 2, 1, true>(p, pl.grid, s); else launch_v2<4, 1, 2, 1, false>(p, pl.grid, s);
-  } else if (pl.nt == 64 && !pl.wres && pl.th == 16) {
-    launch_v2<4, 1, 4, 2, false>(p, pl.grid, s);
+    rc = pl.wres ? launch_v2<4, 1, 2, 1, true>(p, g, s) : launch_v2<4, 1, 2, 1, false>(p, g, s);
+  } else if (pl.nt == 64 && pl.th == 16) {
+    rc = launch_v2<4, 1, 4, 2, false>(p, g, s);
   } else if (pl.nt == 64) {
-    if (pl.wres) launch_v2<2, 2, 4, 1, true>(p, pl.grid, s); else launch_v2<2, 2, 4, 1, false>(p, pl.grid, s);
+    rc = pl.wres ? launch_v2<2, 2, 4, 1, true>(p, g, s) : launch_v2<2, 2, 4, 1, false>(p, g, s);
   } else {
-    launch_v2<2, 2, 4, 2, false>(p, pl.grid, s);
+    rc = launch_v2<2, 2, 4, 2, false>(p, g, s);
   }
-  int rc = oct_check_launch("igemm2");
-  return rc ? rc : 1;
+  return rc ? rc : oct_check_launch("igemm2");
 }

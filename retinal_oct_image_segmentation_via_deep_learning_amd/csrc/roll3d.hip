@@ -17,7 +17,6 @@
 // No reference counterpart (the volumetric network is BASELINE configs[4]); bit-exact against torch's float64 Conv3d on
 // exactly representable operands (tests/test_gpu_exact.py).
 #include "common.h"
-#include <stdlib.h>
 
 struct RollParams {
   const bf16_t* x; const float* sc; const float* sh; const bf16_t* wp;
@@ -322,64 +321,38 @@ __global__ void __launch_bounds__(512) roll3d_kernel(const RollParams p) {
   }
 }
 
-static bool roll_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("OCT_ROLL3D");
-    const char* v2 = getenv("OCT_DISABLE_V2");
-    on = ((e && e[0] == '0') || (v2 && v2[0] == '1')) ? 0 : 1;
-  }
-  return on == 1;
-}
-
 // Which launches: measured on cfg5 (profiles/r03_cfg5_kernel_table.txt, same box): 32 -> 32 forward with BatchNorm sums 4.9 -> 3.96 ms,
 // the 32 -> 64 data gradient 7.6 -> 6.6 ms, but the 32 -> 32 data gradient (no sums) 3.25 -> 3.97 ms -- igemm2's 16-row tile gives
 // each weight fragment four MFMAs, the 8-row tile the ring forces (four 16-row slice tiles do not fit the LDS) only two, and at
 // Cout = 32 all four MFMA waves stream the SAME 54 KB of filter per item: 62 B/clk per CU of L2 requests beside 128 B/clk of LDS
-// reads, both at the CU's limits.  Those stay on igemm2 (OCT_ROLL3D=2 forces every eligible launch here).
-static bool roll_ok(const OctConvDesc* d) {
-  static int all = -1;
-  if (all < 0) { const char* e = getenv("OCT_ROLL3D"); all = (e && e[0] == '2') ? 1 : 0; }
-  if (!all && d->cout == 32 && !d->want_stats) return false;
-  return roll_enabled() && d->dtype == OCT_DT_BF16 && d->depth > 0 && d->taps == 9 && d->kh != 7 && d->in_mode == OCT_IN_PLAIN &&
-         d->out_mode == OCT_OUT_PLAIN && d->c0 == 32 && d->c1 == 0 && (d->cout == 32 || d->cout == 64) &&
-         (d->split == 0 || (d->cout == 64 && d->split == 32)) && (d->w % 32) == 0 && (d->h % 8) == 0 && (d->n % d->depth) == 0 &&
-         d->out_img_mul == 0 && d->depth >= 2 && (size_t)d->n * d->h * d->w < (1ull << 31);
-}
-static int roll_grid(const OctConvDesc* d) {
+// reads, both at the CU's limits.  Those stay on igemm2.
+bool roll3d_plan(const OctConvDesc* d, ConvPlan* pl) {
+  if (d->cout == 32 && !d->want_stats) return false;
+  if (!(d->dtype == OCT_DT_BF16 && d->depth > 0 && d->taps == 9 && d->kh != 7 && d->in_mode == OCT_IN_PLAIN &&
+        d->out_mode == OCT_OUT_PLAIN && d->c0 == 32 && d->c1 == 0 && (d->cout == 32 || d->cout == 64) &&
+        (d->split == 0 || (d->cout == 64 && d->split == 32)) && (d->w % 32) == 0 && (d->h % 8) == 0 && (d->n % d->depth) == 0 &&
+        d->out_img_mul == 0 && d->depth >= 2 && (size_t)d->n * d->h * d->w < (1ull << 31)))
+    return false;
   const int ncols = (d->w / 32) * (d->h / 8) * (d->n / d->depth);
-  return ncols < 256 ? ncols : 256;   // one persistent workgroup per CU (the ring fills the LDS)
+  pl->path = CONV_ROLL3D;
+  pl->grid = pl->stat_rows = ncols < 256 ? ncols : 256;   // one persistent workgroup per CU (the ring fills the LDS)
+  return true;
 }
 
-// BatchNorm partial rows the rolling kernel writes for this descriptor, or -1 when it does not take it
-int oct_conv_roll3d_stat_rows(const OctConvDesc* d) { return roll_ok(d) ? roll_grid(d) : -1; }
-
-template <int WM, int WN, int MF>
-static void launch_roll(const RollParams& p, int grid, bool stats, hipStream_t s) {
+template <int WM, int WN, int MF, bool STATS>
+static int launch_roll(const RollParams& p, int grid, hipStream_t s) {
   constexpr int lds = 4 * (10 * 34 * 80) + 64 * 4 + 4 * 32 * 80 + WM * 2 * (WN * 32) * 4;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&roll3d_kernel<WM, WN, MF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&roll3d_kernel<WM, WN, MF, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
-  if (stats) hipLaunchKernelGGL((roll3d_kernel<WM, WN, MF, true>), dim3(grid), dim3(512), lds, s, p);
-  else hipLaunchKernelGGL((roll3d_kernel<WM, WN, MF, false>), dim3(grid), dim3(512), lds, s, p);
+  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&roll3d_kernel<WM, WN, MF, STATS>), lds)) return rc;
+  hipLaunchKernelGGL((roll3d_kernel<WM, WN, MF, STATS>), dim3(grid), dim3(512), lds, s, p);
+  return oct_check_launch("roll3d");
 }
 
-// returns 1 when the launch was taken, 0 when the shape is not eligible, <0 on error
-int oct_conv_forward_roll3d(const OctConvDesc* d, const OctConvArgs* a, void* stream) {
-  if (!roll_ok(d)) return 0;
-  if (d->xform0 && (!a->scale0 || !a->shift0)) return 0;
+int launch_roll3d(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s) {
   RollParams p;
   p.x = (const bf16_t*)a->x0; p.sc = a->scale0; p.sh = a->shift0; p.wp = (const bf16_t*)a->wpacked;
   p.y0 = (bf16_t*)a->y0; p.y1 = (bf16_t*)a->y1; p.stats = d->want_stats ? a->stat_partials : nullptr;
   p.nvol = d->n / d->depth; p.depth = d->depth; p.h = d->h; p.w = d->w; p.cout = d->cout; p.split = d->split; p.xf = d->xform0;
   p.tiles_x = d->w / 32; p.tiles_y = d->h / 8; p.ncols = p.tiles_x * p.tiles_y * p.nvol;
-  const int grid = roll_grid(d);
-  hipStream_t s = as_stream(stream);
-  if (d->cout == 32) launch_roll<4, 1, 2>(p, grid, p.stats != nullptr, s);
-  else launch_roll<2, 2, 4>(p, grid, p.stats != nullptr, s);
-  const int rc = oct_check_launch("roll3d");
-  return rc ? rc : 1;
+  if (d->cout == 32) return launch_roll<4, 1, 2, true>(p, pl.grid, s);   // Cout = 32 takes the launches with BatchNorm sums only
+  return p.stats ? launch_roll<2, 2, 4, true>(p, pl.grid, s) : launch_roll<2, 2, 4, false>(p, pl.grid, s);
 }

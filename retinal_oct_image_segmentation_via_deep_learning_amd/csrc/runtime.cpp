@@ -3,6 +3,9 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+#include <mutex>
+#include <set>
+#include <utility>
 #include "../../include/oct_hip.h"
 
 static thread_local char g_err[512] = "";
@@ -21,6 +24,26 @@ int oct_check_launch(const char* what) {
     return OCT_E_LAUNCH;
   }
   return OCT_OK;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device setting: remembered per (device, kernel), set under a lock
+int oct_lds_optin(const void* kernel, int bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<int, const void*>> done;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) {
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({dev, kernel})) return OCT_OK;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) {
+      done.insert({dev, kernel});
+      return OCT_OK;
+    }
+  }
+  (void)hipGetLastError();
+  oct_set_error("opting a kernel in to %d bytes of LDS failed: %s", bytes, hipGetErrorString(e));
+  return OCT_E_LAUNCH;
 }
 
 extern "C" {

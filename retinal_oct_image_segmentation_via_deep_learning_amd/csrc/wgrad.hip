@@ -203,38 +203,20 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgradParams p) {
   }
 }
 
-extern "C" int oct_conv_wgrad(const OctWgradDesc* d, const OctWgradArgs* a, void* stream) {
-  OCT_CHECK(d && a, "oct_conv_wgrad: null descriptor");
-  OCT_CHECK(d->dtype == OCT_DT_BF16 || d->dtype == OCT_DT_F32, "oct_conv_wgrad: bad dtype %d", d->dtype);
-  int kh = 0, kw = 0;
-  OCT_CHECK(oct_conv_kernel_size(d->taps, d->kh, d->kw, &kh, &kw),
-            "oct_conv_wgrad: kernel must be 3x3 (taps 9), 1x1 (taps 1) or 7x3 (taps 21, kh=7, kw=3); got taps=%d kh=%d kw=%d",
-            d->taps, d->kh, d->kw);
-  OCT_CHECK(kh != 7 || (d->dy_mode == OCT_IN_PLAIN && !a->dy_coef), "oct_conv_wgrad: 7x3 takes a plain dY");
-  OCT_CHECK(d->depth >= 0 && (d->depth == 0 || ((d->n % d->depth) == 0 && kh != 7)), "oct_conv_wgrad: bad depth %d for n=%d", d->depth, d->n);
-  OCT_CHECK(((d->in_img_shift >= -1 && d->in_img_shift <= 1) || d->in_img_shift == OCT_IMG_SHIFT_ALL) && (d->in_img_shift == 0 || d->depth > 0),
-            "oct_conv_wgrad: in_img_shift needs depth > 0");
-  OCT_CHECK(d->in_img_shift != OCT_IMG_SHIFT_ALL || oct_conv_wgrad_all_depth_taps_ok(d),
-            "oct_conv_wgrad: OCT_IMG_SHIFT_ALL is not available for this descriptor (oct_conv_wgrad_all_depth_taps_ok)");
-  OCT_CHECK(d->dy_img_mul == 0 || d->dy_mode == OCT_IN_S2D, "oct_conv_wgrad: the dY image map belongs to S2D");
-  OCT_CHECK(d->n > 0 && d->h > 0 && d->w > 0 && d->c0 > 0 && d->c1 >= 0 && d->cout > 0, "oct_conv_wgrad: bad shape");
-  OCT_CHECK(a->x0 && a->dy && a->dwp, "oct_conv_wgrad: null tensor");
-  OCT_CHECK(d->c1 == 0 || a->x1, "oct_conv_wgrad: c1 > 0 but x1 is null");
-  OCT_CHECK(!(d->dy_mode == OCT_IN_S2D && (d->cout & 3)), "oct_conv_wgrad: S2D dy needs cout %% 4 == 0");
-  OCT_CHECK(d->xform0 >= 0 && d->xform0 <= OCT_XF_AFFINE && d->xform1 >= 0 && d->xform1 <= OCT_XF_AFFINE, "oct_conv_wgrad: bad xform");
-  OCT_CHECK(!(d->xform0 && (!a->scale0 || !a->shift0)), "oct_conv_wgrad: xform0 without scale/shift");
-  OCT_CHECK(!(d->xform1 && (!a->scale1 || !a->shift1)), "oct_conv_wgrad: xform1 without scale/shift");
-  OCT_CHECK(!d->partials || !a->dbias || a->dbias_partials, "oct_conv_wgrad: partials mode with a bias gradient needs dbias_partials");
-  if (kh != 7) {
-    int took = oct_first_wgrad(d, a, stream);
-    if (took == 0 && a->dy_coef) OCT_CHECK(false, "oct_conv_wgrad: the fused BN-backward apply is only implemented for the 1->F first layer in bf16");
-    if (took == 0) took = oct_conv_wgrad_v2(d, a, stream);
-    if (took != 0) return took < 0 ? took : OCT_OK;
-  } else {
-    int took = oct_first_wgrad(d, a, stream);            // Conv2d(1 -> F, 7x3): the matrix-pipe first-layer kernel
-    if (took == 0) took = oct_conv_wgrad_v2(d, a, stream);   // 64-channel-block shapes: three row-shifted launches of the 3x3 kernel
-    if (took != 0) return took < 0 ? took : OCT_OK;
-  }
+// persistent workgroups: ~4 per CU over all channel-block pairs; a slab per (workgroup column, wave) in partials mode
+void wgrad_plan(const OctWgradDesc* d, WgradPlan* pl) {
+  const int nco = ceil_div(d->cout, 32), nci = ceil_div(d->c0 + d->c1, 32);
+  const int ntiles = ceil_div(d->w, 32) * ceil_div(d->h, 8) * d->n;
+  int per_pair = 1024 / (nco * nci);
+  if (per_pair < 1) per_pair = 1;
+  if (per_pair > ntiles) per_pair = ntiles;
+  pl->path = WGRAD_GENERIC;
+  pl->grid = per_pair;
+  pl->slabs = per_pair * 4;
+}
+
+int launch_wgrad(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s) {
+  const int kh = d->taps == 21 ? 7 : d->taps == 9 ? 3 : 1, kw = d->taps == 1 ? 1 : 3;
   WgradParams p;
   p.x0 = a->x0; p.x1 = a->x1; p.sc0 = a->scale0; p.sh0 = a->shift0; p.sc1 = a->scale1; p.sh1 = a->shift1;
   p.dy = a->dy; p.dwp = a->dwp; p.dbias = a->dbias;
@@ -242,65 +224,25 @@ extern "C" int oct_conv_wgrad(const OctWgradDesc* d, const OctWgradArgs* a, void
   p.xf0 = d->xform0; p.xf1 = d->xform1; p.dy_mode = d->dy_mode;
   p.depth = d->depth; p.img_shift = d->in_img_shift; p.dy_mul = d->dy_img_mul; p.dy_add = d->dy_img_add;
   p.tiles_x = ceil_div(d->w, 32); p.tiles_y = ceil_div(d->h, 8); p.ntiles = p.tiles_x * p.tiles_y * d->n;
-  const int nco = ceil_div(d->cout, 32), nci = ceil_div(p.ktot, 32);
-  // persistent workgroups: ~4 per CU over all channel-block pairs
-  int per_pair = 1024 / (nco * nci);
-  if (per_pair < 1) per_pair = 1;
-  if (per_pair > p.ntiles) per_pair = p.ntiles;
-  dim3 grid(per_pair, nco, nci);
+  const dim3 grid(pl.grid, ceil_div(d->cout, 32), ceil_div(p.ktot, 32));
   p.part_mode = d->partials ? 1 : 0; p.slab_elems = (size_t)d->taps * d->cout * p.ktot; p.dbias_part = a->dbias_partials;
   const int esz = d->dtype == OCT_DT_BF16 ? 2 : 4;
   const int pixe = 32 + 8 / esz * 2;
   p.pad_h = (kh - 1) / 2; p.pad_w = (kw - 1) / 2;
-  hipStream_t s = as_stream(stream);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<float, 3, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<float, 1, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<float, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    attr_set = true;
-  }
   const bool bf = d->dtype == OCT_DT_BF16;
   for (int ty0 = 0; ty0 < kh; ty0 += 3) {
     const int tr = kh - ty0 >= 3 ? 3 : 1;           // kh in {1, 3, 7}: groups of three rows, then single rows
     p.ty0 = ty0;
     if (ty0 > 0) p.dbias = nullptr;                  // the bias gradient belongs to one launch only
     const size_t lds = (size_t)((8 + tr - 1) * (32 + kw - 1) + 8 * 32) * pixe * esz;
-    if (tr == 3 && kw == 3) {
-      if (bf) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 3, 3>), grid, dim3(256), lds, s, p);
-      else hipLaunchKernelGGL((wgrad_kernel<float, 3, 3>), grid, dim3(256), lds, s, p);
-    } else if (tr == 1 && kw == 3) {
-      if (bf) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1, 3>), grid, dim3(256), lds, s, p);
-      else hipLaunchKernelGGL((wgrad_kernel<float, 1, 3>), grid, dim3(256), lds, s, p);
-    } else {
-      if (bf) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1, 1>), grid, dim3(256), lds, s, p);
-      else hipLaunchKernelGGL((wgrad_kernel<float, 1, 1>), grid, dim3(256), lds, s, p);
-    }
+    const auto kern = tr == 3 && kw == 3 ? (bf ? wgrad_kernel<bf16_t, 3, 3> : wgrad_kernel<float, 3, 3>)
+                    : tr == 1 && kw == 3 ? (bf ? wgrad_kernel<bf16_t, 1, 3> : wgrad_kernel<float, 1, 3>)
+                                         : (bf ? wgrad_kernel<bf16_t, 1, 1> : wgrad_kernel<float, 1, 1>);
+    if (!bf)   // fp32 tiles exceed 64 KB
+      if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), 100 * 1024)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
   }
   return oct_check_launch("wgrad");
-}
-
-// Number of partial slabs a launch with this descriptor writes in partials mode (OctWgradDesc.partials = 1): the caller
-// sizes dwp as [slabs][taps][cout][ktot] (and dbias_partials as [slabs][cout]) and hands `slabs` to the unpack pass.
-extern "C" int oct_conv_wgrad_partials(const OctWgradDesc* d) {
-  if (!d) return 0;
-  int kh = 0, kw = 0;
-  if (!oct_conv_kernel_size(d->taps, d->kh, d->kw, &kh, &kw)) return 0;
-  int q = 0;
-  if (kh != 7) {
-    if (oct_first_wgrad(d, nullptr, nullptr, &q) == 1) return q;
-    if (oct_conv_wgrad_v2(d, nullptr, nullptr, &q) == 1) return q;
-  } else {
-    if (oct_first_wgrad(d, nullptr, nullptr, &q) == 1) return q;
-    if (oct_conv_wgrad_v2(d, nullptr, nullptr, &q) == 1) return q;
-  }
-  const int ktot = d->c0 + d->c1;
-  const int nco = ceil_div(d->cout, 32), nci = ceil_div(ktot, 32);
-  const int ntiles = ceil_div(d->w, 32) * ceil_div(d->h, 8) * d->n;
-  int per_pair = 1024 / (nco * nci);
-  if (per_pair < 1) per_pair = 1;
-  if (per_pair > ntiles) per_pair = ntiles;
-  return per_pair * 4;
 }
 
 // dwp[slab][tap][rows][kch] -> torch-layout gradient; the slabs (1 for the atomics mode) are summed in index order.

@@ -14,7 +14,6 @@
 //  * each MFMA wave keeps all 9 tap accumulators of one 32(co) x 32(ci) block (144 registers)
 //    across the whole persistent tile loop and issues its fp32 atomics once at the end.
 #include "common.h"
-#include <stdlib.h>
 
 struct Wgrad2Params {
   const bf16_t* x0; const bf16_t* x1;
@@ -622,64 +621,90 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
 #endif
 }
 
-static bool w2_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("OCT_DISABLE_V2"); on = (e && e[0] == '1') ? 0 : 1; }
-  return on == 1;
+// Persistent grid of one launch: 2 workgroups per CU when the LDS allows (the row-shifted 7x3 launches call this per launch)
+struct W2Grid { int gx, per_wg, interleave; };
+static constexpr int w2_stage(int taps, int cb, int ib, int th) {
+  return ib * (th + 2 * (taps == 9 ? 1 : 0)) * (32 + 2 * (taps != 1 ? 1 : 0)) * 64 + cb * th * 32 * 64;
+}
+static W2Grid w2_grid(int taps, int cb, int ib, int th, int nco, int nci, int n, int h, int w) {
+  const int ntiles = ((w + 31) / 32) * ((h + th - 1) / th) * n;
+  W2Grid g;
+  g.gx = (2 * w2_stage(taps, cb, ib, th) * 2 <= 160 * 1024 ? 512 : 256) / ((nco / cb) * (nci / ib));
+  if (g.gx < 1) g.gx = 1;
+  if (g.gx > ntiles) g.gx = ntiles;
+  g.per_wg = (ntiles + g.gx - 1) / g.gx;
+  g.interleave = ntiles >= 2 * g.gx ? 1 : 0;
+  if (!g.interleave) g.gx = (ntiles + g.per_wg - 1) / g.per_wg;
+  return g;
 }
 
 template <int TAPS, int CB, int IB, int TH, bool RAGGED, bool D3 = false, bool RSH = false>
-static void launch_w2r(Wgrad2Params& p, int nco, int nci, hipStream_t s) {
-  constexpr int halo = TAPS != 1 ? 1 : 0, halo_y = TAPS == 9 ? 1 : 0;
-  constexpr int stage = IB * (TH + 2 * halo_y) * (32 + 2 * halo) * 64 + CB * TH * 32 * 64;
-  constexpr int lds = 2 * stage + 2 * 32 * IB * (int)sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad2_kernel<TAPS, CB, IB, TH, RAGGED, D3, RSH>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
+static int launch_w2r(Wgrad2Params& p, int nco, int nci, hipStream_t s) {
+  constexpr int lds = 2 * w2_stage(TAPS, CB, IB, TH) + 2 * 32 * IB * (int)sizeof(float);
+  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&wgrad2_kernel<TAPS, CB, IB, TH, RAGGED, D3, RSH>), lds)) return rc;
+  const W2Grid g = w2_grid(TAPS, CB, IB, TH, nco, nci, p.n, p.h, p.w);
   p.tiles_x = (p.w + 31) / 32; p.tiles_y = (p.h + TH - 1) / TH; p.ntiles = p.tiles_x * p.tiles_y * p.n;
-  const int gy = nco / CB, gz = nci / IB;
-  int gx = (2 * stage * 2 <= 160 * 1024 ? 512 : 256) / (gy * gz);  // 2 workgroups per CU when LDS allows
-  if (gx < 1) gx = 1;
-  if (gx > p.ntiles) gx = p.ntiles;
-  p.per_wg = (p.ntiles + gx - 1) / gx;
-  p.interleave = p.ntiles >= 2 * gx ? 1 : 0;
-  if (!p.interleave) gx = (p.ntiles + p.per_wg - 1) / p.per_wg;
-  if (p.part_mode < 0) { p.part_mode = gx * (CB * IB > 4 ? 1 : 4 / (CB * IB)); return; }   // query: slabs this launch would write
-  hipLaunchKernelGGL((wgrad2_kernel<TAPS, CB, IB, TH, RAGGED, D3, RSH>), dim3(gx, gy, gz), dim3(512), lds, s, p);
+  p.per_wg = g.per_wg; p.interleave = g.interleave;
+  hipLaunchKernelGGL((wgrad2_kernel<TAPS, CB, IB, TH, RAGGED, D3, RSH>), dim3(g.gx, nco / CB, nci / IB), dim3(512), lds, s, p);
+  return OCT_OK;
 }
 template <int TAPS, int CB, int IB, int TH>
-static void launch_w2(Wgrad2Params& p, int nco, int nci, hipStream_t s) {
+static int launch_w2(Wgrad2Params& p, int nco, int nci, hipStream_t s) {
   // whole tiles take the instantiation without the dY validity mask (no register cost on the bench shapes)
   const bool whole = (p.w % 32) == 0 && (p.h % TH) == 0;
-  if (p.depth > 0 || p.dy_mul) launch_w2r<TAPS, CB, IB, TH, false, true>(p, nco, nci, s);   // volumetric: whole tiles (checked by the caller)
-  else if (whole) launch_w2r<TAPS, CB, IB, TH, false>(p, nco, nci, s);
-  else launch_w2r<TAPS, CB, IB, TH, true>(p, nco, nci, s);
+  if (p.depth > 0 || p.dy_mul) return launch_w2r<TAPS, CB, IB, TH, false, true>(p, nco, nci, s);   // volumetric: whole tiles (wgrad2_plan)
+  if (whole) return launch_w2r<TAPS, CB, IB, TH, false>(p, nco, nci, s);
+  return launch_w2r<TAPS, CB, IB, TH, true>(p, nco, nci, s);
 }
 
-// returns 1 when taken, 0 when the shape is not eligible, <0 on error; query != nullptr: no launch, *query = number
-// of partial slabs the launch would write in partials mode
-int oct_conv_wgrad_v2(const OctWgradDesc* d, const OctWgradArgs* a, void* stream, int* query) {
-  if (!w2_enabled()) return 0;
+bool wgrad2_plan(const OctWgradDesc* d, WgradPlan* pl) {
   if (d->kh == 7) {
     // 7x3 (ReLayNet): 64 x 64 channel blocks, atomics mode only; everything else stays on the generic kernel
     if (d->taps != 21 || d->kw != 3 || d->depth > 0 || d->dy_img_mul != 0 || d->dy_mode != OCT_IN_PLAIN || d->partials ||
         d->dtype != OCT_DT_BF16 || (d->c0 % 32) != 0 || (d->c1 % 32) != 0 || (d->cout % 64) != 0 || ((d->c0 + d->c1) % 64) != 0)
-      return 0;
+      return false;
   }
-  if ((d->depth > 0 || d->dy_img_mul != 0) && ((d->w % 32) != 0 || (d->h % 16) != 0)) return 0;   // volumetric: whole tiles
-  const int ktot = d->c0 + d->c1;
+  if ((d->depth > 0 || d->dy_img_mul != 0) && ((d->w % 32) != 0 || (d->h % 16) != 0)) return false;   // volumetric: whole tiles
   // plain 3x3 / 1x1: any H, W (ragged last tiles are predicated); the deconv mode needs whole tiles
   const bool whole = (d->w % 32) == 0 && (d->h % 8) == 0;
   const bool ok = d->dtype == OCT_DT_BF16 && (whole || d->dy_mode == OCT_IN_PLAIN) && (d->c0 % 32) == 0 &&
                   (d->c1 % 32) == 0 && (d->cout % 32) == 0 &&
                   (d->dy_mode == OCT_IN_PLAIN || ((d->cout >> 2) % 32) == 0);
-  if (!ok) return 0;
+  if (!ok) return false;
+  const int nco = d->cout / 32, nci = (d->c0 + d->c1) / 32;
+  const bool big = (nco % 2 == 0) && (nci % 2 == 0);
+  int cb = 1, ib = 1, th = 8;
+  if (d->kh == 7) {
+    cb = ib = 2;   // three row-shifted launches of the nine-tap kernel (launch_wgrad2)
+  } else if (d->taps == 9) {
+    // 64 x 64 channel blocks: 8-row tiles (halo overhead 10/8 instead of 6/4 on the staged input, half the
+    // barriers; the two 76-KB stage buffers fill the LDS and the producer ring drops to 2 stages): -5 %
+    // 32 x 32 channel blocks (the 32-channel full-resolution layers): 16-row tiles, halo overhead 18/16 -- -6 %
+    // 32 x 64 / 64 x 32 channel blocks (an odd block count on one side: Cout = 32 with Cin = 64, Cin = 32 with Cout = 64 --
+    // dec1 conv1, enc2 conv1): two pairs per workgroup share the staged tile of the 32-channel side, which 1 x 1 blocks
+    // read twice (the 64 -> 32 layer at 512 x 1024: 4.3 GB per launch instead of 3.2)
+    const bool pairs = (d->h % 8) == 0 && d->dy_img_mul == 0;
+    if (big) cb = ib = 2;
+    else if (pairs && nci % 2 == 0) ib = 2;
+    else if (pairs && nco % 2 == 0) cb = 2;
+    else th = 16;
+  } else {
+    const bool m_ok = nco % 4 == 0 && (d->h % 4) == 0 && d->depth == 0 && d->dy_img_mul == 0;
+    if (m_ok && nci % 4 == 0) { cb = ib = 4; th = 4; }    // 128 x 128 channel blocks, 4-row tiles
+    else if (m_ok && nci % 2 == 0) { cb = 4; ib = 2; th = 4; }   // 128 x 64 (upconv1: Cin = 64)
+    else if (big) cb = ib = 2;
+    // else 32 x 32 blocks, 8 rows: -14 % vs 4
+  }
+  pl->path = WGRAD_W2;
+  pl->cb = cb; pl->ib = ib; pl->th = th;
+  // partials mode: one slab per (workgroup column, row strip); the 7x3 launches run in atomics mode only
+  pl->slabs = w2_grid(d->taps == 1 ? 1 : 9, cb, ib, th, nco, nci, d->n, d->h, d->w).gx * (cb * ib > 4 ? 1 : 4 / (cb * ib));
+  return true;
+}
+
+int launch_wgrad2(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s) {
+  const int ktot = d->c0 + d->c1;
   Wgrad2Params p;
-  static const OctWgradArgs no_args = {};
-  if (query) a = &no_args;
   p.x0 = (const bf16_t*)a->x0; p.x1 = (const bf16_t*)a->x1;
   p.sc0 = a->scale0; p.sh0 = a->shift0; p.sc1 = a->scale1; p.sh1 = a->shift1;
   p.dy = (const bf16_t*)a->dy; p.dwp = a->dwp; p.dbias = a->dbias;
@@ -688,56 +713,37 @@ int oct_conv_wgrad_v2(const OctWgradDesc* d, const OctWgradArgs* a, void* stream
 #else
   p.trace = nullptr;
 #endif
-  p.part_mode = query ? -1 : (d->partials ? 1 : 0);
+  p.part_mode = d->partials ? 1 : 0;
   p.slab_elems = (size_t)d->taps * d->cout * ktot; p.dbias_part = a->dbias_partials;
-  if (p.part_mode == 1 && a->dbias && !a->dbias_partials) { oct_set_error("oct_conv_wgrad: partials mode with a bias gradient needs dbias_partials"); return OCT_E_INVALID; }
   p.n = d->n; p.h = d->h; p.w = d->w; p.c0 = d->c0; p.c1 = d->c1; p.ktot = ktot; p.cout = d->cout;
   p.xf0 = d->xform0; p.xf1 = d->xform1; p.dy_mode = d->dy_mode;
   p.depth = d->depth; p.img_shift = d->in_img_shift; p.dy_mul = d->dy_img_mul; p.dy_add = d->dy_img_add;
   const int nco = d->cout / 32, nci = ktot / 32;
-  const bool big = (nco % 2 == 0) && (nci % 2 == 0);
-  hipStream_t s = as_stream(stream);
   p.ty0 = 0; p.pad_y = 1; p.nstore = 9;
+  int rc = OCT_OK;
   if (d->kh == 7) {
     // three launches: tap rows 0-2 and 3-5 on the nine-tap kernel, row 6 on its one-row (three-tap) form (the first version ran
     // row 6 on the nine-tap kernel too and dropped two rows of accumulators: 27 taps of MFMA work for 21); the bias gradient
     // rides on the first
     const bool whole = (p.w % 32) == 0 && (p.h % 8) == 0;
     float* const dwp0 = p.dwp;
-    for (int ty0 = 0; ty0 < 7; ty0 += 3) {
+    for (int ty0 = 0; ty0 < 7 && rc == OCT_OK; ty0 += 3) {
       p.ty0 = ty0; p.pad_y = 3; p.nstore = ty0 == 6 ? 3 : 9;
       p.dwp = dwp0 + (size_t)ty0 * 3 * d->cout * ktot;
       if (ty0 > 0) p.dbias = nullptr;
-      if (ty0 == 6) {
-        if (whole) launch_w2r<3, 2, 2, 8, false, false, true>(p, nco, nci, s);
-        else launch_w2r<3, 2, 2, 8, true, false, true>(p, nco, nci, s);
-      } else if (whole) launch_w2r<9, 2, 2, 8, false, false, true>(p, nco, nci, s);
-      else launch_w2r<9, 2, 2, 8, true, false, true>(p, nco, nci, s);
-      if (query) break;
+      if (ty0 == 6) rc = whole ? launch_w2r<3, 2, 2, 8, false, false, true>(p, nco, nci, s) : launch_w2r<3, 2, 2, 8, true, false, true>(p, nco, nci, s);
+      else rc = whole ? launch_w2r<9, 2, 2, 8, false, false, true>(p, nco, nci, s) : launch_w2r<9, 2, 2, 8, true, false, true>(p, nco, nci, s);
     }
   } else if (d->taps == 9) {
-    // 64 x 64 channel blocks: 8-row tiles (halo overhead 10/8 instead of 6/4 on the staged input, half the
-    // barriers; the two 76-KB stage buffers fill the LDS and the producer ring drops to 2 stages): -5 %
-    // 32 x 32 channel blocks (the 32-channel full-resolution layers): 16-row tiles, halo overhead 18/16 -- -6 %
-    // 32 x 64 / 64 x 32 channel blocks (an odd block count on one side: Cout = 32 with Cin = 64, Cin = 32 with Cout = 64 --
-    // dec1 conv1, enc2 conv1): two pairs per workgroup share the staged tile of the 32-channel side, which 1 x 1 blocks
-    // read twice (the 64 -> 32 layer at 512 x 1024: 4.3 GB per launch instead of 3.2)
-    static int pairs2 = -1;
-    if (pairs2 < 0) { const char* e = getenv("OCT_W2_PAIRS2"); pairs2 = (e && e[0] == '0') ? 0 : 1; }
-    if (big) launch_w2<9, 2, 2, 8>(p, nco, nci, s);
-    else if (pairs2 && nci % 2 == 0 && (d->h % 8) == 0 && d->dy_img_mul == 0) launch_w2<9, 1, 2, 8>(p, nco, nci, s);
-    else if (pairs2 && nco % 2 == 0 && (d->h % 8) == 0 && d->dy_img_mul == 0) launch_w2<9, 2, 1, 8>(p, nco, nci, s);
-    else launch_w2<9, 1, 1, 16>(p, nco, nci, s);
+    if (pl.cb == 2 && pl.ib == 2) rc = launch_w2<9, 2, 2, 8>(p, nco, nci, s);
+    else if (pl.ib == 2) rc = launch_w2<9, 1, 2, 8>(p, nco, nci, s);
+    else if (pl.cb == 2) rc = launch_w2<9, 2, 1, 8>(p, nco, nci, s);
+    else rc = launch_w2<9, 1, 1, 16>(p, nco, nci, s);
   } else {
-    static int multi = -1;
-    if (multi < 0) { const char* e = getenv("OCT_W2_MULTI"); multi = (e && e[0] == '0') ? 0 : 1; }
-    const bool m_ok = multi && nco % 4 == 0 && (d->h % 4) == 0 && d->depth == 0 && d->dy_img_mul == 0;
-    if (m_ok && nci % 4 == 0) launch_w2<1, 4, 4, 4>(p, nco, nci, s);        // 128 x 128 channel blocks, 4-row tiles
-    else if (m_ok && nci % 2 == 0) launch_w2<1, 4, 2, 4>(p, nco, nci, s);   // 128 x 64 (upconv1: Cin = 64)
-    else if (big) launch_w2<1, 2, 2, 8>(p, nco, nci, s);
-    else launch_w2<1, 1, 1, 8>(p, nco, nci, s);   // 8 rows: -14 % vs 4
+    if (pl.cb == 4 && pl.ib == 4) rc = launch_w2<1, 4, 4, 4>(p, nco, nci, s);
+    else if (pl.cb == 4) rc = launch_w2<1, 4, 2, 4>(p, nco, nci, s);
+    else if (pl.cb == 2) rc = launch_w2<1, 2, 2, 8>(p, nco, nci, s);
+    else rc = launch_w2<1, 1, 1, 8>(p, nco, nci, s);
   }
-  if (query) { *query = p.part_mode; return 1; }
-  int rc = oct_check_launch("wgrad2");
-  return rc ? rc : 1;
+  return rc ? rc : oct_check_launch("wgrad2");
 }

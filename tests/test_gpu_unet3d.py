@@ -110,7 +110,7 @@ ROLL = [(5, 3, 128, 128, 32, 0, "relu"), (2, 2, 8, 32, 32, 0, None), (1, 7, 24, 
 @pytest.mark.parametrize("shape", ROLL)
 def test_conv3d_depth_rolling_kernel_bit_exact(env, shape):
     """3x3x3 convolution of 32 channels on the depth-rolling kernel against torch's float64 conv3d on exactly representable
-    operands: output, BatchNorm sums, and the same launch with OCT_ROLL3D-ineligible routing (igemm2's depth-tap mode) as a
+    operands: output, BatchNorm sums, and the same launch with roll3d-ineligible routing (igemm2's depth-tap mode) as a
     second witness.  No reference counterpart (parity unpinned by the reference)."""
     L, E = env
     b, d, h, w, cout, split, xf = shape
