@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCT_VERSION 220 /* 0.2.2 (round 3): 7x3 on the pipelined kernels, oct_rowdot_* up to 12 outputs, frozen-BatchNorm backward, depth-rolling 3-D kernel; 0.2.1: + oct_bilinear_resize_*, floor-mode max-pooling (MGU-Net); 0.2.0: (kh,kw) kernels, depth taps, partials, ReLayNet / 3-D / per-class metric entry points */
+#define OCT_VERSION 220 /* 0.2.2 (round 3; + oct_seg_loss_*: CE / Dice on network logits, NHWC or NCHW): 7x3 on the pipelined kernels, oct_rowdot_* up to 12 outputs, frozen-BatchNorm backward, depth-rolling 3-D kernel; 0.2.1: + oct_bilinear_resize_*, floor-mode max-pooling (MGU-Net); 0.2.0: (kh,kw) kernels, depth taps, partials, ReLayNet / 3-D / per-class metric entry points */
 
 /* dtypes of activation storage */
 #define OCT_DT_BF16 0
@@ -336,6 +336,35 @@ int oct_head_backward_fused(const OctHeadDesc* d, const void* y, const float* sc
                             const int64_t* target, const float* dice_coef, float w_ce,
                             const float* dprobs, void* dlogits, void* da, float* partials,
                             float* dbias, float* dweight, double* loss_partials, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Segmentation loss on logits a network has already produced (U_Net / AttU_Net / AttU_Net4,
+ * MGUNet / MGUNet_2, ReLayNet: the networks without the fused head above).  Same loss as the
+ * head's -- CE = mean over pixels of -log softmax[target], Dice = 1 - mean_c (2 I_c + eps) /
+ * (P_c + Y_c + eps) -- and the same partial rows, so oct_head_loss_finalize reduces them
+ * (descriptor: feat = 1).  d->dtype / n / h / w / classes describe the logits; d->feat is not
+ * read here.  No atomics: per-lane, wave, workgroup sums, one fp64 row per workgroup.
+ *   layout OCT_SEG_NHWC: logits [n,h,w,classes] in d->dtype (the networks' own output)
+ *   layout OCT_SEG_NCHW: logits [n,classes,h,w] fp32 (what a network's forward returns)
+ * A target outside [0, classes) makes the loss NaN (no check, no synchronisation).
+ * ------------------------------------------------------------------------------------------ */
+#define OCT_SEG_NHWC 0
+#define OCT_SEG_NCHW 1
+/* rows of loss_partials the two launches below write (0 for npix == 0 or classes out of [1,16]) */
+int oct_seg_loss_blocks(size_t npix, int classes);
+/* argmax (int64 [n,h,w], may be NULL): first maximum of the logits wins, as in torch.argmax;
+ * loss_partials (may be NULL, needs target): [oct_seg_loss_blocks][OCT_HEAD_LOSS_SLOTS].
+ * target == NULL with argmax only is a pure predict.                                            */
+int oct_seg_loss_forward(const OctHeadDesc* d, int layout, const void* logits, const int64_t* target,
+                         int64_t* argmax, double* loss_partials, void* stream);
+/* dlogits (same layout and dtype as the logits) = g * [w_ce (p - onehot)/N + p (dp - <p,dp>)]
+ * with dp_c = A_c onehot_c + B_c from oct_head_loss_finalize's dice_coef (NULL: no Dice term)
+ * and g = *dloss (device float, NULL: 1).  loss_partials (only with dice_coef == NULL, may be
+ * NULL): the cross-entropy rows as well -- slot 0 filled, the Dice slots zero -- so a CE-only
+ * training step reads the logits once and feeds these rows to oct_head_loss_finalize.          */
+int oct_seg_loss_backward(const OctHeadDesc* d, int layout, const void* logits, const int64_t* target,
+                          const float* dice_coef, float w_ce, const float* dloss, void* dlogits,
+                          double* loss_partials, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Layout / dtype helpers and the optimizer

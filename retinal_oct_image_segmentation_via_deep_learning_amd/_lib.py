@@ -25,6 +25,7 @@ PACK_CONV_FPROP, PACK_CONV_DGRAD, PACK_DECONV_FPROP, PACK_DECONV_DGRAD, PACK_1X1
 PACK_CONV3D_FPROP, PACK_CONV3D_DGRAD, PACK_DECONV3D_FPROP, PACK_DECONV3D_DGRAD = 6, 7, 8, 9
 MAX_CLASSES = 16
 HEAD_LOSS_SLOTS = 2 + 3 * MAX_CLASSES
+SEG_NHWC, SEG_NCHW = 0, 1   # oct_seg_loss_* logits layouts (OCT_SEG_NHWC / OCT_SEG_NCHW)
 
 c_void_p, c_int, c_size_t, c_float, c_double = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_double
 
@@ -144,6 +145,10 @@ SIGNATURES = {
     "oct_head_backward_fused": (c_int, [C.POINTER(HeadDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_seg_loss_blocks": (c_int, [c_size_t, c_int]),
+    "oct_seg_loss_forward": (c_int, [C.POINTER(HeadDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_seg_loss_backward": (c_int, [C.POINTER(HeadDesc), c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
     "oct_nchw_to_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "oct_nhwc_to_nchw": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "oct_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_int,

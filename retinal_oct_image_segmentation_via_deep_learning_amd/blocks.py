@@ -17,6 +17,7 @@ from torch.nn import init
 
 from . import _lib as L
 from . import ops
+from .losses import SegLossMixin
 
 
 class HipModule(nn.Module):
@@ -269,8 +270,9 @@ class Attention_block(HipModule):
 # ------------------------------------------------------------------------------------------------
 # SD_Layer_Net/unet.py
 # ------------------------------------------------------------------------------------------------
-class _SDUNetBase(HipModule):
+class _SDUNetBase(SegLossMixin, HipModule):
     _levels = 5
+    _head = "Conv_1x1"
 
     def _encode(self, a):
         dt = self.compute_dtype
@@ -282,7 +284,7 @@ class _SDUNetBase(HipModule):
             feats.append(a)
         return feats
 
-    def forward(self, x):
+    def _logits_nhwc(self, x):
         if x.dim() != 4:
             raise RuntimeError(f"expected a 4-D (B,C,H,W) input, got {tuple(x.shape)}")
         div = 1 << (self._levels - 1)
@@ -300,7 +302,10 @@ class _SDUNetBase(HipModule):
             if att is not None:
                 skip = att.nhwc(d, skip)
             d = getattr(self, f"Up_conv{i}").nhwc(skip, d)      # torch.cat((skip, d), dim=1)
-        return self._out(ops.conv_bn_act(self.compute_dtype, d, self.Conv_1x1))
+        return ops.conv_bn_act(self.compute_dtype, d, self.Conv_1x1)
+
+    def forward(self, x):
+        return self._out(self._logits_nhwc(x))
 
 
 class U_Net(_SDUNetBase):

@@ -1,0 +1,296 @@
+// Cross-entropy + soft-Dice loss on logits that a network has already produced (U_Net, AttU_Net, MGU-Net, ReLayNet: every
+// network whose class head is not the fused UNet head of head.hip).  Two layouts, one per-pixel code path:
+//   NHWC in the compute dtype (what the networks write) -- a block's 256 pixels are one contiguous span of 256 * classes
+//     elements: it is staged through LDS with 16-B loads (and d(loss)/d(logits) leaves the same way), so a 3-class bf16 row of
+//     6 B never turns into 2-B scalar accesses;
+//   NCHW fp32 (what every network's forward returns) -- per class, consecutive lanes read consecutive addresses.
+// The forward writes per-workgroup fp64 rows in head_fwd_kernel's layout [OCT_HEAD_LOSS_SLOTS], so oct_head_loss_finalize
+// turns them into [loss, ce, dice] and the Dice backward coefficients unchanged.  The reduction order is fixed: per-lane sums,
+// wave sums, workgroup sums, one row per workgroup -- no atomics.
+#include "common.h"
+
+#define SEG_THREADS 256
+#define SEG_MAX_GRID 1024
+
+struct SegParams {
+  const void* logits; const int64_t* target; int64_t* argmax; double* loss_partials;
+  const float* dice_coef; const float* dloss; void* dlogits; float w_ce;
+  size_t npix, hw; int classes; int vec_in, vec_out;
+};
+
+// one tile = SEG_THREADS consecutive pixels, one per lane.  NHWC: the tile's span of the tensor goes through `stage` with
+// 16-B accesses (the span starts 16-B aligned: 256 * classes * sizeof(T) is a multiple of 16; vec = base pointer aligned too)
+template <typename T>
+__device__ __forceinline__ void stage_copy(T* __restrict__ dst, const T* __restrict__ src, int ne, bool vec) {
+  int done = 0;
+  if (vec) {
+    const int nq = (int)((ne * sizeof(T)) >> 4);
+    for (int i = threadIdx.x; i < nq; i += SEG_THREADS)
+      reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+    done = (int)((nq * 16) / sizeof(T));
+  }
+  for (int i = done + threadIdx.x; i < ne; i += SEG_THREADS) dst[i] = src[i];
+}
+
+template <bool NCHW, typename T, int CMAX>
+__device__ __forceinline__ void seg_load(const SegParams& p, size_t p0, int np, T* stage, float (&l)[CMAX]) {
+  const int C = p.classes;
+  const size_t pix = p0 + threadIdx.x;
+  const bool live = threadIdx.x < np;
+  if (NCHW) {
+    const float* x = reinterpret_cast<const float*>(p.logits);
+    const size_t img = live ? pix / p.hw : 0, off = live ? pix - img * p.hw : 0;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) l[c] = (live && c < C) ? x[(img * C + c) * p.hw + off] : 0.f;
+  } else {
+    stage_copy<T>(stage, reinterpret_cast<const T*>(p.logits) + p0 * C, np * C, p.vec_in);
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) l[c] = (live && c < C) ? to_f32(stage[threadIdx.x * C + c]) : 0.f;
+  }
+}
+
+template <int CMAX>
+__device__ __forceinline__ void seg_softmax(int classes, const float (&l)[CMAX], float (&pr)[CMAX], float& m, float& lse) {
+  m = l[0];
+#pragma unroll
+  for (int c = 1; c < CMAX; ++c)
+    if (c < classes) m = fmaxf(m, l[c]);
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) {
+    pr[c] = (c < classes) ? expf(l[c] - m) : 0.f;
+    s += pr[c];
+  }
+  const float inv = 1.f / s;
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) pr[c] *= inv;
+  lse = logf(s);
+}
+
+// -log softmax[t] of one pixel; NaN for a label outside [0, classes) (torch's nll_loss raises there; no synchronisation here)
+template <int CMAX>
+__device__ __forceinline__ float seg_ce(int classes, int t, const float (&l)[CMAX], float m, float lse) {
+  float lt = 0.f;
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) lt = (c == t) ? l[c] : lt;
+  return (unsigned)t < (unsigned)classes ? -(lt - m - lse) : __builtin_nanf("");
+}
+
+// wave -> workgroup -> one fp64 row per workgroup (head_fwd_kernel's layout: [ce, 0, I_c..., P_c..., Y_c...])
+template <int CMAX>
+__device__ __forceinline__ void seg_write_row(double* __restrict__ row, float ce, const float (&si)[CMAX], const float (&sp)[CMAX],
+                                              const float (&sy)[CMAX], bool dice, double (&red)[SEG_THREADS / 64][OCT_HEAD_LOSS_SLOTS]) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double v = wave_sum((double)ce);
+  if (lane == 0) { red[wave][0] = v; red[wave][1] = 0.0; }
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) {
+    const double a = dice ? wave_sum((double)si[c]) : 0.0, b = dice ? wave_sum((double)sp[c]) : 0.0,
+                 d = dice ? wave_sum((double)sy[c]) : 0.0;
+    if (lane == 0) {
+      red[wave][2 + c] = a; red[wave][2 + OCT_MAX_CLASSES + c] = b; red[wave][2 + 2 * OCT_MAX_CLASSES + c] = d;
+    }
+  }
+  if (lane == 0)
+    for (int c = CMAX; c < OCT_MAX_CLASSES; ++c) {
+      red[wave][2 + c] = 0.0; red[wave][2 + OCT_MAX_CLASSES + c] = 0.0; red[wave][2 + 2 * OCT_MAX_CLASSES + c] = 0.0;
+    }
+  __syncthreads();
+  for (int i = threadIdx.x; i < OCT_HEAD_LOSS_SLOTS; i += SEG_THREADS) {
+    double s = 0.0;
+    for (int wv = 0; wv < SEG_THREADS / 64; ++wv) s += red[wv][i];
+    row[i] = s;
+  }
+}
+
+template <typename T, int CMAX>
+struct SegStage { T v[SEG_THREADS * CMAX]; };
+
+template <bool NCHW, typename T, int CMAX>
+__global__ void __launch_bounds__(SEG_THREADS) seg_fwd_kernel(const SegParams p) {
+  __shared__ __attribute__((aligned(16))) SegStage<T, NCHW ? 1 : CMAX> stage;
+  __shared__ double red[SEG_THREADS / 64][OCT_HEAD_LOSS_SLOTS];
+  const int C = p.classes;
+  float ce = 0.f, si[CMAX], sp[CMAX], sy[CMAX];
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) { si[c] = 0.f; sp[c] = 0.f; sy[c] = 0.f; }
+  const size_t ntiles = (p.npix + SEG_THREADS - 1) / SEG_THREADS;
+  for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const size_t p0 = tile * SEG_THREADS, pix = p0 + threadIdx.x;
+    const int np = (int)(p.npix - p0 < SEG_THREADS ? p.npix - p0 : SEG_THREADS);
+    float l[CMAX];
+    seg_load<NCHW, T, CMAX>(p, p0, np, stage.v, l);
+    if (threadIdx.x < np) {
+      if (p.argmax) {   // on the logits, first maximum wins and NaN beats everything (torch.argmax)
+        int best = 0; float bv = l[0];
+#pragma unroll
+        for (int c = 1; c < CMAX; ++c)
+          if (c < C && (l[c] > bv || (l[c] != l[c] && bv == bv))) { bv = l[c]; best = c; }
+        p.argmax[pix] = best;
+      }
+      if (p.loss_partials) {
+        float pr[CMAX], m, lse;
+        seg_softmax<CMAX>(C, l, pr, m, lse);
+        const int t = (int)p.target[pix];
+        ce += seg_ce<CMAX>(C, t, l, m, lse);
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) {
+          const bool hit = (c == t);
+          si[c] += hit ? pr[c] : 0.f;
+          sp[c] += pr[c];
+          sy[c] += hit ? 1.f : 0.f;
+        }
+      }
+    }
+    if (!NCHW) __syncthreads();   // the next tile overwrites the stage
+  }
+  if (p.loss_partials) seg_write_row<CMAX>(p.loss_partials + (size_t)blockIdx.x * OCT_HEAD_LOSS_SLOTS, ce, si, sp, sy, true, red);
+}
+
+// d(loss)/d(logits) = g * [w_ce (p - onehot) / N + p (dp - <p, dp>)], dp_c = A_c [c == t] + B_c from the finalize kernel's
+// dice_coef (no Dice term without it) -- oct_head_dlogits's formula; g = *dloss (1 without it), read here so that an autograd
+// backward never synchronises.  loss_partials (only without a Dice term): the CE rows as well, so the CE-only step reads the
+// logits once.
+template <bool NCHW, typename T, int CMAX>
+__global__ void __launch_bounds__(SEG_THREADS) seg_bwd_kernel(const SegParams p) {
+  __shared__ __attribute__((aligned(16))) SegStage<T, NCHW ? 1 : CMAX> stage;
+  __shared__ double red[SEG_THREADS / 64][OCT_HEAD_LOSS_SLOTS];
+  const int C = p.classes;
+  float dcA[CMAX], dcB[CMAX];
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) {
+    dcA[c] = (p.dice_coef && c < C) ? p.dice_coef[c] : 0.f;
+    dcB[c] = (p.dice_coef && c < C) ? p.dice_coef[OCT_MAX_CLASSES + c] : 0.f;
+  }
+  const float g = p.dloss ? *p.dloss : 1.f;
+  const float inv_n = 1.f / (float)p.npix;
+  float ce = 0.f;
+  T* out = reinterpret_cast<T*>(p.dlogits);
+  const size_t ntiles = (p.npix + SEG_THREADS - 1) / SEG_THREADS;
+  for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const size_t p0 = tile * SEG_THREADS, pix = p0 + threadIdx.x;
+    const int np = (int)(p.npix - p0 < SEG_THREADS ? p.npix - p0 : SEG_THREADS);
+    float l[CMAX], pr[CMAX], dl[CMAX], m, lse;
+    seg_load<NCHW, T, CMAX>(p, p0, np, stage.v, l);
+    const bool live = threadIdx.x < np;
+    const int t = live ? (int)p.target[pix] : 0;
+    seg_softmax<CMAX>(C, l, pr, m, lse);
+    {
+      float dp[CMAX], dot = 0.f;
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c) {
+        dp[c] = (c == t ? dcA[c] : 0.f) + dcB[c];
+        dot = fmaf(pr[c], dp[c], dot);
+      }
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c) dl[c] = (p.w_ce * (pr[c] - (c == t ? 1.f : 0.f)) * inv_n + pr[c] * (dp[c] - dot)) * g;
+    }
+    if (p.loss_partials && live) ce += seg_ce<CMAX>(C, t, l, m, lse);
+    if (NCHW) {
+      if (live) {
+        float* o = reinterpret_cast<float*>(p.dlogits);
+        const size_t img = pix / p.hw, off = pix - img * p.hw;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+          if (c < C) o[(img * C + c) * p.hw + off] = dl[c];
+      }
+    } else {
+      __syncthreads();   // every lane has read its logits from the stage
+      if (live) {
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+          if (c < C) stage.v[threadIdx.x * C + c] = from_f32<T>(dl[c]);
+      }
+      __syncthreads();
+      stage_copy<T>(out + p0 * C, stage.v, np * C, p.vec_out);
+      __syncthreads();   // the next tile overwrites the stage
+    }
+  }
+  if (p.loss_partials) {
+    float z[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) z[c] = 0.f;
+    seg_write_row<CMAX>(p.loss_partials + (size_t)blockIdx.x * OCT_HEAD_LOSS_SLOTS, ce, z, z, z, false, red);
+  }
+}
+
+extern "C" int oct_seg_loss_blocks(size_t npix, int classes) {
+  if (npix == 0 || classes < 1 || classes > OCT_MAX_CLASSES) return 0;
+  const size_t tiles = (npix + SEG_THREADS - 1) / SEG_THREADS;
+  return (int)(tiles < SEG_MAX_GRID ? tiles : SEG_MAX_GRID);
+}
+
+static int seg_check(const OctHeadDesc* d, int layout, const char* who) {
+  OCT_CHECK(d, "%s: null descriptor", who);
+  OCT_CHECK(layout == OCT_SEG_NHWC || layout == OCT_SEG_NCHW, "%s: bad layout %d (OCT_SEG_NHWC or OCT_SEG_NCHW)", who, layout);
+  OCT_CHECK(d->dtype == OCT_DT_BF16 || d->dtype == OCT_DT_F32, "%s: bad dtype %d", who, d->dtype);
+  OCT_CHECK(layout == OCT_SEG_NHWC || d->dtype == OCT_DT_F32, "%s: NCHW logits are fp32 only", who);
+  OCT_CHECK(d->n > 0 && d->h > 0 && d->w > 0, "%s: bad shape", who);
+  OCT_CHECK(d->classes > 0 && d->classes <= OCT_MAX_CLASSES, "%s: classes %d not in [1,%d]", who, d->classes, OCT_MAX_CLASSES);
+  return OCT_OK;
+}
+
+static SegParams seg_params(const OctHeadDesc* d, const void* logits) {
+  SegParams p = {};
+  p.logits = logits;
+  p.hw = (size_t)d->h * d->w;
+  p.npix = (size_t)d->n * p.hw;
+  p.classes = d->classes;
+  p.vec_in = ((uintptr_t)logits & 15) == 0;
+  return p;
+}
+
+#define SEG_DISPATCH(KERNEL, d, layout, grid, s, p)                                                              \
+  do {                                                                                                           \
+    const int cm = (d)->classes <= 2 ? 2 : (d)->classes <= 4 ? 4 : (d)->classes <= 8 ? 8 : 16;                   \
+    const dim3 gd(grid), bd(SEG_THREADS);                                                                        \
+    if ((layout) == OCT_SEG_NCHW) {                                                                              \
+      if (cm == 2) hipLaunchKernelGGL((KERNEL<true, float, 2>), gd, bd, 0, s, p);                                \
+      else if (cm == 4) hipLaunchKernelGGL((KERNEL<true, float, 4>), gd, bd, 0, s, p);                           \
+      else if (cm == 8) hipLaunchKernelGGL((KERNEL<true, float, 8>), gd, bd, 0, s, p);                           \
+      else hipLaunchKernelGGL((KERNEL<true, float, 16>), gd, bd, 0, s, p);                                       \
+    } else if ((d)->dtype == OCT_DT_BF16) {                                                                      \
+      if (cm == 2) hipLaunchKernelGGL((KERNEL<false, bf16_t, 2>), gd, bd, 0, s, p);                              \
+      else if (cm == 4) hipLaunchKernelGGL((KERNEL<false, bf16_t, 4>), gd, bd, 0, s, p);                         \
+      else if (cm == 8) hipLaunchKernelGGL((KERNEL<false, bf16_t, 8>), gd, bd, 0, s, p);                         \
+      else hipLaunchKernelGGL((KERNEL<false, bf16_t, 16>), gd, bd, 0, s, p);                                     \
+    } else {                                                                                                     \
+      if (cm == 2) hipLaunchKernelGGL((KERNEL<false, float, 2>), gd, bd, 0, s, p);                               \
+      else if (cm == 4) hipLaunchKernelGGL((KERNEL<false, float, 4>), gd, bd, 0, s, p);                          \
+      else if (cm == 8) hipLaunchKernelGGL((KERNEL<false, float, 8>), gd, bd, 0, s, p);                          \
+      else hipLaunchKernelGGL((KERNEL<false, float, 16>), gd, bd, 0, s, p);                                      \
+    }                                                                                                            \
+  } while (0)
+
+extern "C" int oct_seg_loss_forward(const OctHeadDesc* d, int layout, const void* logits, const int64_t* target,
+                                    int64_t* argmax, double* loss_partials, void* stream) {
+  int rc = seg_check(d, layout, "oct_seg_loss_forward");
+  if (rc) return rc;
+  OCT_CHECK(logits, "oct_seg_loss_forward: null pointer (logits)");
+  OCT_CHECK(argmax || loss_partials, "oct_seg_loss_forward: null pointer (neither argmax nor loss_partials)");
+  OCT_CHECK(!loss_partials || target, "oct_seg_loss_forward: null pointer (loss partials need a target)");
+  SegParams p = seg_params(d, logits);
+  p.target = target; p.argmax = argmax; p.loss_partials = loss_partials;
+  const int grid = oct_seg_loss_blocks(p.npix, d->classes);
+  hipStream_t s = as_stream(stream);
+  SEG_DISPATCH(seg_fwd_kernel, d, layout, grid, s, p);
+  return oct_check_launch("seg_loss_fwd");
+}
+
+extern "C" int oct_seg_loss_backward(const OctHeadDesc* d, int layout, const void* logits, const int64_t* target,
+                                     const float* dice_coef, float w_ce, const float* dloss, void* dlogits,
+                                     double* loss_partials, void* stream) {
+  int rc = seg_check(d, layout, "oct_seg_loss_backward");
+  if (rc) return rc;
+  OCT_CHECK(logits && target && dlogits, "oct_seg_loss_backward: null pointer (logits, target and dlogits are required)");
+  OCT_CHECK(!(loss_partials && dice_coef), "oct_seg_loss_backward: CE rows come from the backward only without a Dice term");
+  SegParams p = seg_params(d, logits);
+  p.target = target; p.dice_coef = dice_coef; p.w_ce = w_ce; p.dloss = dloss; p.dlogits = dlogits;
+  p.loss_partials = loss_partials;
+  p.vec_out = ((uintptr_t)dlogits & 15) == 0;
+  const int grid = oct_seg_loss_blocks(p.npix, d->classes);
+  hipStream_t s = as_stream(stream);
+  SEG_DISPATCH(seg_bwd_kernel, d, layout, grid, s, p);
+  return oct_check_launch("seg_loss_bwd");
+}

@@ -192,17 +192,25 @@ class DataParallelTrainer:
     exchange (then ONE bucket after the replay) and the one-kernel optimizer step stay outside the
     graph.  Capture happens on the first step() after `graph_warmup` eager steps (the optimizer's
     first-step flag and the weight re-packing that follows every update must already be in their
-    steady state)."""
+    steady state).
+
+    Models without an engine (the logits networks of blocks.py, mgunet.py, relaynet.py: losses.SegLossMixin) run their
+    backward through autograd, which has no stage boundaries to hook: their gradient leaves as ONE bucket after backward,
+    and use_graph is refused."""
 
     def __init__(self, model, lr=0.01, momentum=0.9, weight_decay=0.0, w_ce=1.0, w_dice=0.0, use_graph=False,
                  graph_warmup=2, bucket_cap_bytes=3 << 20, always_communicate=False):
         from .optim import FusedSGD
+        staged = hasattr(model, "_engine")
+        if use_graph and not staged:
+            raise NotImplementedError(f"use_graph=True needs an engine network (UNet, BioUNet, UNet3D); {type(model).__name__} "
+                                      "runs its backward through autograd, which is not captured in a graph")
         self.model = model
         self.opt = FusedSGD(list(model.named_parameters()), lr=lr, momentum=momentum, weight_decay=weight_decay)
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         broadcast_parameters(self.opt.flat_p)
         broadcast_buffers(model)
-        buckets = None if use_graph else bucket_plan_for(model, self.opt.layout, bucket_cap_bytes)
+        buckets = bucket_plan_for(model, self.opt.layout, bucket_cap_bytes) if staged and not use_graph else None
         self.reducer = GradAllReducer(self.opt.flat_g, self.world, buckets, always_communicate=always_communicate)
         self.w_ce, self.w_dice = w_ce, w_dice
         self.use_graph, self.graph_warmup = use_graph, graph_warmup

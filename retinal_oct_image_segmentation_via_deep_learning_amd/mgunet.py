@@ -18,6 +18,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .blocks import HipModule, UnetConv, UnetUp, UnetUp4, init_weights
+from .losses import SegLossMixin
 
 
 class Basconv(HipModule):
@@ -112,8 +113,9 @@ class MGR_Module(HipModule):
         return self._out(self.nhwc(self._in(x)))
 
 
-class _MGUNetBase(HipModule):
+class _MGUNetBase(SegLossMixin, HipModule):
     _pools = (2, 2, 2)
+    _head = "final_1"
 
     def __init__(self, in_channels=1, num_classes=11, feature_scale=4, is_deconv=True, is_batchnorm=True, compute_dtype="bf16"):
         super().__init__()
@@ -146,7 +148,7 @@ class _MGUNetBase(HipModule):
             elif isinstance(m, nn.BatchNorm2d):
                 init_weights(m, init_type="kaiming")
 
-    def forward(self, inputs):
+    def _logits_nhwc(self, inputs):
         dt = self.compute_dtype
         ops.prepack(dt, self)
         p1, p2, p3 = self._pools
@@ -158,7 +160,10 @@ class _MGUNetBase(HipModule):
         up3 = self.up_concat3.nhwc(center, conv3)
         up2 = self.up_concat2.nhwc(up3, conv2)
         up1 = self.up_concat1.nhwc(up2, conv1)
-        return self._out(ops.conv_bn_act(dt, up1, self.final_1))
+        return ops.conv_bn_act(dt, up1, self.final_1)
+
+    def forward(self, inputs):
+        return self._out(self._logits_nhwc(inputs))
 
 
 class MGUNet(_MGUNetBase):

@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from . import ops
 from .blocks import HipModule
+from .losses import SegLossMixin
 
 
 def _nchw_idx(idx_nhwc):
@@ -118,7 +119,9 @@ class ClassifierBlock(HipModule):
         return self._out(self.nhwc(self._in(input)))
 
 
-class ReLayNet(HipModule):
+class ReLayNet(SegLossMixin, HipModule):
+    _head = "classifier.conv"
+
     def __init__(self, in_channels=1, num_classes=10, num_filters=64, kernel_h=7, kernel_w=3, stride_conv=1, pool=2,
                  stride_pool=2, compute_dtype="bf16"):
         super().__init__()
@@ -137,7 +140,7 @@ class ReLayNet(HipModule):
         self.classifier = ClassifierBlock(dict(wide, num_class=num_classes), compute_dtype)
         self._div = pool ** 3
 
-    def forward(self, input):
+    def _logits_nhwc(self, input):
         if input.dim() != 4:
             raise RuntimeError(f"expected a 4-D (B,C,H,W) input, got {tuple(input.shape)}")
         if input.shape[2] % self._div or input.shape[3] % self._div:
@@ -154,7 +157,10 @@ class ReLayNet(HipModule):
         d3 = self.decode1.nhwc(bn, out3, ind3)
         d2 = self.decode2.nhwc(d3, out2, ind2)
         d1 = self.decode3.nhwc(d2, out1, ind1)
-        return self._out(self.classifier.nhwc(d1))
+        return self.classifier.nhwc(d1)
+
+    def forward(self, input):
+        return self._out(self._logits_nhwc(input))
 
     @property
     def is_cuda(self):

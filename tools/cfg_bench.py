@@ -1,47 +1,111 @@
-"""Throughput of the parity configurations (not the bench line): cfg1 BioNet UNet(1,2) 4x256x256 and
-cfg4 AttU_Net(1,3) 16x496x768, bf16, training step = fwd + CE + bwd + SGD.  usage: cfg_bench.py [steps]"""
-import os, sys, time
+"""Throughput of the parity configurations (not the bench line), bf16, training step = fwd + loss + bwd + SGD(momentum).
+
+  cfg1 BioNet UNet(1,2) 4x256x256 and 32x256x256: forward_backward + FusedSGD (engine network)
+  cfg4 AttU_Net(1,3) 16x496x768, ReLayNet(1,10) 16x496x768, MGUNet_2(1,11) 16x496x768, two ways each, alternating in one
+  process (same seeds, same inputs):
+    torch  -- F.cross_entropy(model(x), t) + torch.optim.SGD: NCHW fp32 logits, ATen log_softmax / nll_loss
+    fused  -- model.forward_backward(x, t) + FusedSGD: the loss kernels on the NHWC logits (losses.py, csrc/seg_loss.hip)
+
+usage: cfg_bench.py [steps] [rounds]     CFG_ONLY=1 / 4 / relaynet / mgunet2 runs one group.
+CFG_PROFILE=1: only the fused cfg4 step, 3 warm-up steps + 1 (for a rocprofv3 --kernel-trace --stats pass)."""
+import os
+import statistics
+import sys
+import time
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch
-import torch.nn.functional as F
-from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Layers_Segment.BioNet_2020 import UNet as BioUNet
-from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Layers_Segment.SD_Layer_Net.unet import AttU_Net
-from retinal_oct_image_segmentation_via_deep_learning_amd.optim import FusedSGD
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Lesions_Segment.ReLayNet_2017 import ReLayNet  # noqa: E402
+from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Layers_Segment.BioNet_2020 import UNet as BioUNet  # noqa: E402
+from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Layers_Segment.MGUNet_2021 import MGUNet_2  # noqa: E402
+from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Layers_Segment.SD_Layer_Net.unet import AttU_Net  # noqa: E402
+from retinal_oct_image_segmentation_via_deep_learning_amd.optim import FusedSGD  # noqa: E402
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+WARMUP = 8     # the autograd-driven networks reach their steady state after ~8 steps (bench.py)
 g = torch.Generator().manual_seed(1234)
 
 
-def run(name, model, x, t, fused):
+def stepper(model, x, t, fused):
     model.cuda().train()
-    opt = FusedSGD(model.parameters(), lr=0.01, momentum=0.9) if fused else torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9)
+    if fused:
+        opt = FusedSGD(list(model.named_parameters()), lr=0.01, momentum=0.9)
 
-    def step():
-        if fused:
+        def step():
             model.forward_backward(x, t)
-        else:
+            opt.step()
+    else:
+        opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9)
+
+        def step():
             opt.zero_grad(set_to_none=True)
             F.cross_entropy(model(x), t).backward()
-        opt.step()
-    for _ in range(3):
-        step()
+            opt.step()
+    return step
+
+
+def timed(step, n):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(n):
         step()
     torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / steps
-    print(f"{name}: {dt * 1e3:.2f} ms/step, {x.shape[0] / dt:.1f} B-scans/s, peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
+    return (time.perf_counter() - t0) / n
+
+
+def run(name, model, x, t):
+    """engine network: forward_backward + FusedSGD only"""
+    step = stepper(model, x, t, True)
+    for _ in range(3):
+        step()
+    dt = timed(step, steps)
+    print(f"{name}: {dt * 1e3:.2f} ms/step, {x.shape[0] / dt:.1f} B-scans/s, peak memory "
+          f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
+
+
+def pair(name, make, x, t):
+    """the torch-CE path and the fused path of two identically seeded models, timed in alternating rounds"""
+    torch.manual_seed(0)
+    st_torch = stepper(make(), x, t, False)
+    torch.manual_seed(0)
+    st_fused = stepper(make(), x, t, True)
+    for _ in range(WARMUP):
+        st_torch()
+        st_fused()
+    ms = {"torch": [], "fused": []}
+    for _ in range(rounds):
+        ms["torch"].append(timed(st_torch, steps) * 1e3)
+        ms["fused"].append(timed(st_fused, steps) * 1e3)
+    a, b = statistics.median(ms["torch"]), statistics.median(ms["fused"])
+    print(f"{name}: torch CE + SGD {a:.2f} ms/step, forward_backward + FusedSGD {b:.2f} ms/step "
+          f"({a - b:+.2f} ms, {a / b:.3f}x; medians of {rounds} rounds x {steps} steps; "
+          f"rounds torch {['%.2f' % v for v in ms['torch']]} fused {['%.2f' % v for v in ms['fused']]})", flush=True)
 
 
 ONLY = os.environ.get("CFG_ONLY", "")
 torch.manual_seed(0)
-x = torch.randn(4, 1, 256, 256, generator=g).cuda(); t = torch.randint(0, 2, (4, 256, 256), generator=g).cuda()
+if os.environ.get("CFG_PROFILE"):
+    x = torch.randn(16, 1, 496, 768, generator=g).cuda()
+    t = torch.randint(0, 3, (16, 496, 768), generator=g).cuda()
+    torch.manual_seed(0)
+    step = stepper(AttU_Net(1, 3), x, t, True)
+    for _ in range(4):
+        step()
+    torch.cuda.synchronize()
+    print("cfg4 fused: 4 steps done")
+    sys.exit(0)
 if ONLY in ("", "1"):
-    run("cfg1 BioNet UNet(1,2) 4x256x256", BioUNet(1, 2), x, t, True)
-x = torch.randn(32, 1, 256, 256, generator=g).cuda(); t = torch.randint(0, 2, (32, 256, 256), generator=g).cuda()
-if ONLY in ("", "1"):
-    run("     BioNet UNet(1,2) 32x256x256", BioUNet(1, 2), x, t, True)
-x = torch.randn(16, 1, 496, 768, generator=g).cuda(); t = torch.randint(0, 3, (16, 496, 768), generator=g).cuda()
-if ONLY in ("", "4"):
-    run("cfg4 AttU_Net(1,3) 16x496x768", AttU_Net(1, 3), x, t, False)
+    x = torch.randn(4, 1, 256, 256, generator=g).cuda(); t = torch.randint(0, 2, (4, 256, 256), generator=g).cuda()
+    run("cfg1 BioNet UNet(1,2) 4x256x256", BioUNet(1, 2), x, t)
+    x = torch.randn(32, 1, 256, 256, generator=g).cuda(); t = torch.randint(0, 2, (32, 256, 256), generator=g).cuda()
+    run("     BioNet UNet(1,2) 32x256x256", BioUNet(1, 2), x, t)
+for key, name, make, ncls in (("4", "cfg4 AttU_Net(1,3) 16x496x768", lambda: AttU_Net(1, 3), 3),
+                              ("relaynet", "ReLayNet(1,10) 16x496x768", lambda: ReLayNet(1, 10), 10),
+                              ("mgunet2", "MGUNet_2(1,11) 16x496x768", lambda: MGUNet_2(1, 11), 11)):
+    if ONLY in ("", key):
+        x = torch.randn(16, 1, 496, 768, generator=g).cuda()
+        t = torch.randint(0, ncls, (16, 496, 768), generator=g).cuda()
+        pair(name, make, x, t)
+        torch.cuda.empty_cache()
