@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCT_VERSION 220 /* 0.2.2 (round 3; + oct_seg_loss_*: CE / Dice on network logits, NHWC or NCHW): 7x3 on the pipelined kernels, oct_rowdot_* up to 12 outputs, frozen-BatchNorm backward, depth-rolling 3-D kernel; 0.2.1: + oct_bilinear_resize_*, floor-mode max-pooling (MGU-Net); 0.2.0: (kh,kw) kernels, depth taps, partials, ReLayNet / 3-D / per-class metric entry points */
+#define OCT_VERSION 220 /* 0.2.2 (round 3; + oct_seg_loss_*: CE / Dice on network logits, NHWC or NCHW; + oct_seg_loss_*_weighted: class weights, pixel weight map, ignore_index): 7x3 on the pipelined kernels, oct_rowdot_* up to 12 outputs, frozen-BatchNorm backward, depth-rolling 3-D kernel; 0.2.1: + oct_bilinear_resize_*, floor-mode max-pooling (MGU-Net); 0.2.0: (kh,kw) kernels, depth taps, partials, ReLayNet / 3-D / per-class metric entry points */
 
 /* dtypes of activation storage */
 #define OCT_DT_BF16 0
@@ -365,6 +365,47 @@ int oct_seg_loss_forward(const OctHeadDesc* d, int layout, const void* logits, c
 int oct_seg_loss_backward(const OctHeadDesc* d, int layout, const void* logits, const int64_t* target,
                           const float* dice_coef, float w_ce, const float* dloss, void* dlogits,
                           double* loss_partials, void* stream);
+
+/* Weighted forms of the loss above (library 0.2.2, same OCT_VERSION): class weights, a per-pixel
+ * weight map and ignore_index, each optional.
+ *   class_weight  float [classes] on the device, NULL: 1
+ *   pixel_weight  float [n,h,w] on the device, NULL: 1 (a constant of the loss: no gradient)
+ *   has_ignore / ignore_index   a pixel whose label equals ignore_index does not count at all
+ *   omega_i = [t_i != ignore_index] * class_weight[t_i] * pixel_weight[i]
+ *   CE   = sum_i omega_i * (-log softmax[t_i]) / sum_i omega_i
+ *          (F.cross_entropy(weight=, ignore_index=) when there is no map)
+ *   Dice = over the pixels that are not ignored, otherwise as above and unweighted
+ * A label outside [0, classes) that is not the ignored one still gives a NaN loss; sum omega = 0
+ * (everything ignored) gives a NaN loss as torch does.  An ignored pixel gets a gradient of
+ * exactly 0 in every class.  sum omega never passes through the host: it is reduced on the device
+ * (oct_seg_loss_weight_sum, or slot 1 of the forward rows -> oct_seg_loss_finalize_weighted's
+ * wsum_out) and oct_seg_loss_backward_weighted reads it there.  No atomics, fixed order.
+ *   CE only:   weight_sum -> backward_weighted(loss_partials = rows) -> finalize_weighted
+ *   with Dice: forward_weighted -> finalize_weighted(wsum_out) -> backward_weighted(dice_coef)  */
+/* sum omega from the labels and the map alone; partials: [oct_seg_loss_blocks] doubles of scratch,
+ * wsum: one double.  d->dtype / layout are not read beyond the usual descriptor checks.          */
+int oct_seg_loss_weight_sum(const OctHeadDesc* d, const int64_t* target, const float* class_weight,
+                            const float* pixel_weight, int has_ignore, int64_t ignore_index,
+                            double* partials, double* wsum, void* stream);
+/* rows [oct_seg_loss_blocks][OCT_HEAD_LOSS_SLOTS]: slot 0 = sum omega*ce, slot 1 = sum omega, then
+ * the Dice sums over the pixels that are not ignored                                             */
+int oct_seg_loss_forward_weighted(const OctHeadDesc* d, int layout, const void* logits,
+                                  const int64_t* target, const float* class_weight,
+                                  const float* pixel_weight, int has_ignore, int64_t ignore_index,
+                                  double* loss_partials, void* stream);
+/* dlogits = g * valid * [w_ce (p - onehot) omega / *wsum + p (dp - <p,dp>)]; wsum: device double.
+ * loss_partials (only with dice_coef == NULL, may be NULL): rows with slots 0 and 1 filled.      */
+int oct_seg_loss_backward_weighted(const OctHeadDesc* d, int layout, const void* logits,
+                                   const int64_t* target, const float* class_weight,
+                                   const float* pixel_weight, int has_ignore, int64_t ignore_index,
+                                   const double* wsum, const float* dice_coef, float w_ce,
+                                   const float* dloss, void* dlogits, double* loss_partials,
+                                   void* stream);
+/* oct_head_loss_finalize with CE = slot 0 / slot 1 instead of slot 0 / N; wsum_out (device double,
+ * may be NULL) receives slot 1's total                                                           */
+int oct_seg_loss_finalize_weighted(const OctHeadDesc* d, const double* loss_partials, int nblocks,
+                                   float w_ce, float w_dice, float dice_eps, float* loss_out,
+                                   float* dice_coef, double* wsum_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Layout / dtype helpers and the optimizer

@@ -7,6 +7,12 @@
 // The forward writes per-workgroup fp64 rows in head_fwd_kernel's layout [OCT_HEAD_LOSS_SLOTS], so oct_head_loss_finalize
 // turns them into [loss, ce, dice] and the Dice backward coefficients unchanged.  The reduction order is fixed: per-lane sums,
 // wave sums, workgroup sums, one row per workgroup -- no atomics.
+// The weighted forms (WEIGHTED = true; oct_seg_loss_*_weighted) scale each pixel's cross-entropy by
+//   omega = [t != ignore_index] * class_weight[t] * pixel_weight[pixel]
+// and divide by sum(omega) instead of N; the Dice sums and gradients run over the pixels that are not ignored.  sum(omega)
+// needs the labels and the map only, so it is reduced first (seg_wsum_kernel) or carried in slot 1 of the forward rows, stays
+// on the device, and the backward kernel reads it there the way it reads *dloss: no host synchronisation, fixed order.
+// The unweighted instantiations are the code they were: every weighted statement sits behind `if constexpr (WEIGHTED)`.
 #include "common.h"
 
 #define SEG_THREADS 256
@@ -16,6 +22,9 @@ struct SegParams {
   const void* logits; const int64_t* target; int64_t* argmax; double* loss_partials;
   const float* dice_coef; const float* dloss; void* dlogits; float w_ce;
   size_t npix, hw; int classes; int vec_in, vec_out;
+  // weighted forms only (each may be null / off)
+  const float* class_weight; const float* pixel_weight; const double* wsum; double* wsum_partials;
+  long long ignore_index; int has_ignore;
 };
 
 // one tile = SEG_THREADS consecutive pixels, one per lane.  NHWC: the tile's span of the tensor goes through `stage` with
@@ -78,12 +87,16 @@ __device__ __forceinline__ float seg_ce(int classes, int t, const float (&l)[CMA
 }
 
 // wave -> workgroup -> one fp64 row per workgroup (head_fwd_kernel's layout: [ce, 0, I_c..., P_c..., Y_c...])
-template <int CMAX>
+// WEIGHTED: slot 1 carries the workgroup's sum of omega (ws)
+template <int CMAX, bool WEIGHTED = false>
 __device__ __forceinline__ void seg_write_row(double* __restrict__ row, float ce, const float (&si)[CMAX], const float (&sp)[CMAX],
-                                              const float (&sy)[CMAX], bool dice, double (&red)[SEG_THREADS / 64][OCT_HEAD_LOSS_SLOTS]) {
+                                              const float (&sy)[CMAX], bool dice, double (&red)[SEG_THREADS / 64][OCT_HEAD_LOSS_SLOTS],
+                                              double ws = 0.0) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const double v = wave_sum((double)ce);
-  if (lane == 0) { red[wave][0] = v; red[wave][1] = 0.0; }
+  double v1 = 0.0;
+  if constexpr (WEIGHTED) v1 = wave_sum(ws);
+  if (lane == 0) { red[wave][0] = v; red[wave][1] = v1; }
 #pragma unroll
   for (int c = 0; c < CMAX; ++c) {
     const double a = dice ? wave_sum((double)si[c]) : 0.0, b = dice ? wave_sum((double)sp[c]) : 0.0,
@@ -107,10 +120,29 @@ __device__ __forceinline__ void seg_write_row(double* __restrict__ row, float ce
 template <typename T, int CMAX>
 struct SegStage { T v[SEG_THREADS * CMAX]; };
 
-template <bool NCHW, typename T, int CMAX>
+// class weights: <= 16 floats, once per workgroup into LDS (1 everywhere without them)
+__device__ __forceinline__ void seg_load_class_weights(const SegParams& p, float* scw) {
+  if (threadIdx.x < OCT_MAX_CLASSES)
+    scw[threadIdx.x] = (p.class_weight && (int)threadIdx.x < p.classes) ? p.class_weight[threadIdx.x] : 1.f;
+  __syncthreads();
+}
+
+// omega of one live pixel and whether it counts at all; the map is read one float per lane next to the label.  A label outside
+// [0, classes) that is not the ignored one keeps weight 1: its cross-entropy is NaN whatever the weight.
+__device__ __forceinline__ float seg_omega(const SegParams& p, const float* scw, size_t pix, long long t64, bool& valid) {
+  valid = !(p.has_ignore && t64 == p.ignore_index);
+  const float pw = p.pixel_weight ? p.pixel_weight[pix] : 1.f;
+  const float cw = (unsigned long long)t64 < (unsigned long long)p.classes ? scw[(int)t64] : 1.f;
+  return valid ? cw * pw : 0.f;
+}
+
+template <bool NCHW, typename T, int CMAX, bool WEIGHTED = false>
 __global__ void __launch_bounds__(SEG_THREADS) seg_fwd_kernel(const SegParams p) {
   __shared__ __attribute__((aligned(16))) SegStage<T, NCHW ? 1 : CMAX> stage;
   __shared__ double red[SEG_THREADS / 64][OCT_HEAD_LOSS_SLOTS];
+  __shared__ float scw[WEIGHTED ? OCT_MAX_CLASSES : 1];
+  if constexpr (WEIGHTED) seg_load_class_weights(p, scw);
+  double ws = 0.0;
   const int C = p.classes;
   float ce = 0.f, si[CMAX], sp[CMAX], sy[CMAX];
 #pragma unroll
@@ -132,30 +164,54 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_fwd_kernel(const SegParams p)
       if (p.loss_partials) {
         float pr[CMAX], m, lse;
         seg_softmax<CMAX>(C, l, pr, m, lse);
-        const int t = (int)p.target[pix];
-        ce += seg_ce<CMAX>(C, t, l, m, lse);
+        if constexpr (WEIGHTED) {
+          const long long t64 = p.target[pix];
+          const int t = (int)t64;
+          bool valid;
+          const float om = seg_omega(p, scw, pix, t64, valid);
+          if (valid) {   // an ignored pixel adds exactly nothing, whatever its logits and label are
+            ce += om * seg_ce<CMAX>(C, t, l, m, lse);
+            ws += (double)om;
 #pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-          const bool hit = (c == t);
-          si[c] += hit ? pr[c] : 0.f;
-          sp[c] += pr[c];
-          sy[c] += hit ? 1.f : 0.f;
+            for (int c = 0; c < CMAX; ++c) {
+              const bool hit = (c == t);
+              si[c] += hit ? pr[c] : 0.f;
+              sp[c] += pr[c];
+              sy[c] += hit ? 1.f : 0.f;
+            }
+          }
+        } else {
+          const int t = (int)p.target[pix];
+          ce += seg_ce<CMAX>(C, t, l, m, lse);
+#pragma unroll
+          for (int c = 0; c < CMAX; ++c) {
+            const bool hit = (c == t);
+            si[c] += hit ? pr[c] : 0.f;
+            sp[c] += pr[c];
+            sy[c] += hit ? 1.f : 0.f;
+          }
         }
       }
     }
     if (!NCHW) __syncthreads();   // the next tile overwrites the stage
   }
-  if (p.loss_partials) seg_write_row<CMAX>(p.loss_partials + (size_t)blockIdx.x * OCT_HEAD_LOSS_SLOTS, ce, si, sp, sy, true, red);
+  if (p.loss_partials)
+    seg_write_row<CMAX, WEIGHTED>(p.loss_partials + (size_t)blockIdx.x * OCT_HEAD_LOSS_SLOTS, ce, si, sp, sy, true, red, ws);
 }
 
 // d(loss)/d(logits) = g * [w_ce (p - onehot) / N + p (dp - <p, dp>)], dp_c = A_c [c == t] + B_c from the finalize kernel's
 // dice_coef (no Dice term without it) -- oct_head_dlogits's formula; g = *dloss (1 without it), read here so that an autograd
 // backward never synchronises.  loss_partials (only without a Dice term): the CE rows as well, so the CE-only step reads the
 // logits once.
-template <bool NCHW, typename T, int CMAX>
+// WEIGHTED: w_ce (p - onehot) omega / sum(omega) with sum(omega) = *wsum read from the device, the Dice term on the pixels that
+// are not ignored, exactly 0 in every class of an ignored pixel; the CE rows then carry sum(omega * ce) and sum(omega).
+template <bool NCHW, typename T, int CMAX, bool WEIGHTED = false>
 __global__ void __launch_bounds__(SEG_THREADS) seg_bwd_kernel(const SegParams p) {
   __shared__ __attribute__((aligned(16))) SegStage<T, NCHW ? 1 : CMAX> stage;
   __shared__ double red[SEG_THREADS / 64][OCT_HEAD_LOSS_SLOTS];
+  __shared__ float scw[WEIGHTED ? OCT_MAX_CLASSES : 1];
+  if constexpr (WEIGHTED) seg_load_class_weights(p, scw);
+  double ws = 0.0;
   const int C = p.classes;
   float dcA[CMAX], dcB[CMAX];
 #pragma unroll
@@ -164,7 +220,7 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_bwd_kernel(const SegParams p)
     dcB[c] = (p.dice_coef && c < C) ? p.dice_coef[OCT_MAX_CLASSES + c] : 0.f;
   }
   const float g = p.dloss ? *p.dloss : 1.f;
-  const float inv_n = 1.f / (float)p.npix;
+  const float inv_n = WEIGHTED ? (float)(1.0 / *p.wsum) : 1.f / (float)p.npix;
   float ce = 0.f;
   T* out = reinterpret_cast<T*>(p.dlogits);
   const size_t ntiles = (p.npix + SEG_THREADS - 1) / SEG_THREADS;
@@ -174,9 +230,27 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_bwd_kernel(const SegParams p)
     float l[CMAX], pr[CMAX], dl[CMAX], m, lse;
     seg_load<NCHW, T, CMAX>(p, p0, np, stage.v, l);
     const bool live = threadIdx.x < np;
-    const int t = live ? (int)p.target[pix] : 0;
+    const long long t64 = live ? p.target[pix] : 0;
+    const int t = (int)t64;
     seg_softmax<CMAX>(C, l, pr, m, lse);
-    {
+    if constexpr (WEIGHTED) {
+      bool valid = false;
+      const float om = live ? seg_omega(p, scw, pix, t64, valid) : 0.f;
+      const float k = om * inv_n;   // omega / sum(omega) in the place of 1 / N, in the unweighted kernel's own expression
+      float dp[CMAX], dot = 0.f;
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c) {
+        dp[c] = (c == t ? dcA[c] : 0.f) + dcB[c];
+        dot = fmaf(pr[c], dp[c], dot);
+      }
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c)
+        dl[c] = valid ? (p.w_ce * (pr[c] - (c == t ? 1.f : 0.f)) * k + pr[c] * (dp[c] - dot)) * g : 0.f;
+      if (p.loss_partials && valid) {
+        ce += om * seg_ce<CMAX>(C, t, l, m, lse);
+        ws += (double)om;
+      }
+    } else {
       float dp[CMAX], dot = 0.f;
 #pragma unroll
       for (int c = 0; c < CMAX; ++c) {
@@ -186,7 +260,8 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_bwd_kernel(const SegParams p)
 #pragma unroll
       for (int c = 0; c < CMAX; ++c) dl[c] = (p.w_ce * (pr[c] - (c == t ? 1.f : 0.f)) * inv_n + pr[c] * (dp[c] - dot)) * g;
     }
-    if (p.loss_partials && live) ce += seg_ce<CMAX>(C, t, l, m, lse);
+    if constexpr (!WEIGHTED)
+      if (p.loss_partials && live) ce += seg_ce<CMAX>(C, t, l, m, lse);
     if (NCHW) {
       if (live) {
         float* o = reinterpret_cast<float*>(p.dlogits);
@@ -211,7 +286,92 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_bwd_kernel(const SegParams p)
     float z[CMAX];
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) z[c] = 0.f;
-    seg_write_row<CMAX>(p.loss_partials + (size_t)blockIdx.x * OCT_HEAD_LOSS_SLOTS, ce, z, z, z, false, red);
+    seg_write_row<CMAX, WEIGHTED>(p.loss_partials + (size_t)blockIdx.x * OCT_HEAD_LOSS_SLOTS, ce, z, z, z, false, red, ws);
+  }
+}
+
+// sum(omega) from the labels and the map alone (12 B per pixel): per-lane fp64 sums, wave, workgroup, one partial per workgroup
+__global__ void __launch_bounds__(SEG_THREADS) seg_wsum_kernel(const SegParams p) {
+  __shared__ float scw[OCT_MAX_CLASSES];
+  __shared__ double red[SEG_THREADS / 64];
+  seg_load_class_weights(p, scw);
+  double ws = 0.0;
+  const size_t ntiles = (p.npix + SEG_THREADS - 1) / SEG_THREADS;
+  for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const size_t pix = tile * SEG_THREADS + threadIdx.x;
+    if (pix < p.npix) {
+      bool valid;
+      ws += (double)seg_omega(p, scw, pix, p.target[pix], valid);
+    }
+  }
+  ws = wave_sum(ws);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ws;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int wv = 0; wv < SEG_THREADS / 64; ++wv) s += red[wv];
+    p.wsum_partials[blockIdx.x] = s;
+  }
+}
+
+// Sum of v[seg], v[seg + 16], ... (n values `stride` doubles apart) in head_loss_finalize_kernel's order: eight independent
+// partial sums keep eight loads in flight instead of one dependent load per round trip, then a fixed tree.  Both reductions
+// below go through it, so sum(omega) has the same bits whether it comes from seg_wsum_kernel's partials or from slot 1 of the rows.
+__device__ __forceinline__ double seg_strided_sum(const double* __restrict__ v, size_t stride, int seg, int n) {
+  double sv[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int b = seg;
+  for (; b + 7 * 16 < n; b += 8 * 16) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) sv[u] += v[(size_t)(b + 16 * u) * stride];
+  }
+  for (; b < n; b += 16) sv[0] += v[(size_t)b * stride];
+  return ((sv[0] + sv[1]) + (sv[2] + sv[3])) + ((sv[4] + sv[5]) + (sv[6] + sv[7]));
+}
+
+// the workgroup partials (<= SEG_MAX_GRID) -> one double on the device
+__global__ void __launch_bounds__(64) seg_wsum_reduce_kernel(const double* __restrict__ partials, int nblocks,
+                                                             double* __restrict__ wsum) {
+  __shared__ double part[16];
+  if (threadIdx.x < 16) part[threadIdx.x] = seg_strided_sum(partials, 1, threadIdx.x, nblocks);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0;
+    for (int k = 0; k < 16; ++k) a += part[k];
+    *wsum = a;
+  }
+}
+
+// head_loss_finalize_kernel's result with CE = sum(omega * ce) / sum(omega): slot 0 over slot 1 of the rows instead of slot 0
+// over N.  Same reduction order, Dice arithmetic and dice_coef; wsum_out (may be null) receives sum(omega) for the backward kernel.
+__global__ void __launch_bounds__(1024) seg_finalize_weighted_kernel(const double* __restrict__ partials, int nblocks, int classes,
+                                                                     float w_ce, float w_dice, float eps, float* loss_out,
+                                                                     float* dice_coef, double* wsum_out) {
+  __shared__ double tot[OCT_HEAD_LOSS_SLOTS];
+  __shared__ double part[16][64];
+  const int slot = threadIdx.x & 63, seg = threadIdx.x >> 6;
+  part[seg][slot] = slot < OCT_HEAD_LOSS_SLOTS ? seg_strided_sum(partials + slot, OCT_HEAD_LOSS_SLOTS, seg, nblocks) : 0.0;
+  __syncthreads();
+  if (threadIdx.x < OCT_HEAD_LOSS_SLOTS) {
+    double a = 0.0;
+    for (int k = 0; k < 16; ++k) a += part[k][slot];
+    tot[threadIdx.x] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double ce = tot[0] / tot[1];   // everything ignored: 0 / 0 = NaN, as torch
+    double dsum = 0.0;
+    for (int c = 0; c < classes; ++c) {
+      const double I = tot[2 + c], P = tot[2 + OCT_MAX_CLASSES + c], Y = tot[2 + 2 * OCT_MAX_CLASSES + c];
+      const double den = P + Y + (double)eps, num = 2.0 * I + (double)eps;
+      dsum += num / den;
+      dice_coef[c] = (float)(-(double)w_dice / classes * 2.0 / den);
+      dice_coef[OCT_MAX_CLASSES + c] = (float)((double)w_dice / classes * num / (den * den));
+    }
+    const double dice = 1.0 - dsum / classes;
+    loss_out[0] = (float)((double)w_ce * ce + (double)w_dice * dice);
+    loss_out[1] = (float)ce;
+    loss_out[2] = (float)dice;
+    if (wsum_out) *wsum_out = tot[1];
   }
 }
 
@@ -241,25 +401,25 @@ static SegParams seg_params(const OctHeadDesc* d, const void* logits) {
   return p;
 }
 
-#define SEG_DISPATCH(KERNEL, d, layout, grid, s, p)                                                              \
+#define SEG_DISPATCH(KERNEL, W, d, layout, grid, s, p)                                                           \
   do {                                                                                                           \
     const int cm = (d)->classes <= 2 ? 2 : (d)->classes <= 4 ? 4 : (d)->classes <= 8 ? 8 : 16;                   \
     const dim3 gd(grid), bd(SEG_THREADS);                                                                        \
     if ((layout) == OCT_SEG_NCHW) {                                                                              \
-      if (cm == 2) hipLaunchKernelGGL((KERNEL<true, float, 2>), gd, bd, 0, s, p);                                \
-      else if (cm == 4) hipLaunchKernelGGL((KERNEL<true, float, 4>), gd, bd, 0, s, p);                           \
-      else if (cm == 8) hipLaunchKernelGGL((KERNEL<true, float, 8>), gd, bd, 0, s, p);                           \
-      else hipLaunchKernelGGL((KERNEL<true, float, 16>), gd, bd, 0, s, p);                                       \
+      if (cm == 2) hipLaunchKernelGGL((KERNEL<true, float, 2, W>), gd, bd, 0, s, p);                             \
+      else if (cm == 4) hipLaunchKernelGGL((KERNEL<true, float, 4, W>), gd, bd, 0, s, p);                        \
+      else if (cm == 8) hipLaunchKernelGGL((KERNEL<true, float, 8, W>), gd, bd, 0, s, p);                        \
+      else hipLaunchKernelGGL((KERNEL<true, float, 16, W>), gd, bd, 0, s, p);                                    \
     } else if ((d)->dtype == OCT_DT_BF16) {                                                                      \
-      if (cm == 2) hipLaunchKernelGGL((KERNEL<false, bf16_t, 2>), gd, bd, 0, s, p);                              \
-      else if (cm == 4) hipLaunchKernelGGL((KERNEL<false, bf16_t, 4>), gd, bd, 0, s, p);                         \
-      else if (cm == 8) hipLaunchKernelGGL((KERNEL<false, bf16_t, 8>), gd, bd, 0, s, p);                         \
-      else hipLaunchKernelGGL((KERNEL<false, bf16_t, 16>), gd, bd, 0, s, p);                                     \
+      if (cm == 2) hipLaunchKernelGGL((KERNEL<false, bf16_t, 2, W>), gd, bd, 0, s, p);                           \
+      else if (cm == 4) hipLaunchKernelGGL((KERNEL<false, bf16_t, 4, W>), gd, bd, 0, s, p);                      \
+      else if (cm == 8) hipLaunchKernelGGL((KERNEL<false, bf16_t, 8, W>), gd, bd, 0, s, p);                      \
+      else hipLaunchKernelGGL((KERNEL<false, bf16_t, 16, W>), gd, bd, 0, s, p);                                  \
     } else {                                                                                                     \
-      if (cm == 2) hipLaunchKernelGGL((KERNEL<false, float, 2>), gd, bd, 0, s, p);                               \
-      else if (cm == 4) hipLaunchKernelGGL((KERNEL<false, float, 4>), gd, bd, 0, s, p);                          \
-      else if (cm == 8) hipLaunchKernelGGL((KERNEL<false, float, 8>), gd, bd, 0, s, p);                          \
-      else hipLaunchKernelGGL((KERNEL<false, float, 16>), gd, bd, 0, s, p);                                      \
+      if (cm == 2) hipLaunchKernelGGL((KERNEL<false, float, 2, W>), gd, bd, 0, s, p);                            \
+      else if (cm == 4) hipLaunchKernelGGL((KERNEL<false, float, 4, W>), gd, bd, 0, s, p);                       \
+      else if (cm == 8) hipLaunchKernelGGL((KERNEL<false, float, 8, W>), gd, bd, 0, s, p);                       \
+      else hipLaunchKernelGGL((KERNEL<false, float, 16, W>), gd, bd, 0, s, p);                                   \
     }                                                                                                            \
   } while (0)
 
@@ -274,7 +434,7 @@ extern "C" int oct_seg_loss_forward(const OctHeadDesc* d, int layout, const void
   p.target = target; p.argmax = argmax; p.loss_partials = loss_partials;
   const int grid = oct_seg_loss_blocks(p.npix, d->classes);
   hipStream_t s = as_stream(stream);
-  SEG_DISPATCH(seg_fwd_kernel, d, layout, grid, s, p);
+  SEG_DISPATCH(seg_fwd_kernel, false, d, layout, grid, s, p);
   return oct_check_launch("seg_loss_fwd");
 }
 
@@ -291,6 +451,78 @@ extern "C" int oct_seg_loss_backward(const OctHeadDesc* d, int layout, const voi
   p.vec_out = ((uintptr_t)dlogits & 15) == 0;
   const int grid = oct_seg_loss_blocks(p.npix, d->classes);
   hipStream_t s = as_stream(stream);
-  SEG_DISPATCH(seg_bwd_kernel, d, layout, grid, s, p);
+  SEG_DISPATCH(seg_bwd_kernel, false, d, layout, grid, s, p);
   return oct_check_launch("seg_loss_bwd");
+}
+
+// ---- weighted forms: class weights, a pixel weight map, ignore_index (each optional) -------------------------------------
+static void seg_weights(SegParams& p, const float* class_weight, const float* pixel_weight, int has_ignore, int64_t ignore_index) {
+  p.class_weight = class_weight; p.pixel_weight = pixel_weight;
+  p.has_ignore = has_ignore != 0; p.ignore_index = (long long)ignore_index;
+}
+
+extern "C" int oct_seg_loss_weight_sum(const OctHeadDesc* d, const int64_t* target, const float* class_weight,
+                                       const float* pixel_weight, int has_ignore, int64_t ignore_index, double* partials,
+                                       double* wsum, void* stream) {
+  int rc = seg_check(d, OCT_SEG_NHWC, "oct_seg_loss_weight_sum");
+  if (rc) return rc;
+  OCT_CHECK(target && partials && wsum, "oct_seg_loss_weight_sum: null pointer (target, partials and wsum are required)");
+  SegParams p = seg_params(d, nullptr);
+  p.target = target; p.wsum_partials = partials;
+  seg_weights(p, class_weight, pixel_weight, has_ignore, ignore_index);
+  const int grid = oct_seg_loss_blocks(p.npix, d->classes);
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(seg_wsum_kernel, dim3(grid), dim3(SEG_THREADS), 0, s, p);
+  hipLaunchKernelGGL(seg_wsum_reduce_kernel, dim3(1), dim3(64), 0, s, partials, grid, wsum);
+  return oct_check_launch("seg_loss_weight_sum");
+}
+
+extern "C" int oct_seg_loss_forward_weighted(const OctHeadDesc* d, int layout, const void* logits, const int64_t* target,
+                                             const float* class_weight, const float* pixel_weight, int has_ignore,
+                                             int64_t ignore_index, double* loss_partials, void* stream) {
+  int rc = seg_check(d, layout, "oct_seg_loss_forward_weighted");
+  if (rc) return rc;
+  OCT_CHECK(logits, "oct_seg_loss_forward_weighted: null pointer (logits)");
+  OCT_CHECK(target && loss_partials, "oct_seg_loss_forward_weighted: null pointer (target and loss_partials are required)");
+  SegParams p = seg_params(d, logits);
+  p.target = target; p.loss_partials = loss_partials;
+  seg_weights(p, class_weight, pixel_weight, has_ignore, ignore_index);
+  const int grid = oct_seg_loss_blocks(p.npix, d->classes);
+  hipStream_t s = as_stream(stream);
+  SEG_DISPATCH(seg_fwd_kernel, true, d, layout, grid, s, p);
+  return oct_check_launch("seg_loss_fwd_weighted");
+}
+
+extern "C" int oct_seg_loss_backward_weighted(const OctHeadDesc* d, int layout, const void* logits, const int64_t* target,
+                                              const float* class_weight, const float* pixel_weight, int has_ignore,
+                                              int64_t ignore_index, const double* wsum, const float* dice_coef, float w_ce,
+                                              const float* dloss, void* dlogits, double* loss_partials, void* stream) {
+  int rc = seg_check(d, layout, "oct_seg_loss_backward_weighted");
+  if (rc) return rc;
+  OCT_CHECK(logits, "oct_seg_loss_backward_weighted: null pointer (logits)");
+  OCT_CHECK(target && dlogits && wsum,
+            "oct_seg_loss_backward_weighted: null pointer (target, dlogits and wsum are required)");
+  OCT_CHECK(!(loss_partials && dice_coef),
+            "oct_seg_loss_backward_weighted: CE rows come from the backward only without a Dice term");
+  SegParams p = seg_params(d, logits);
+  p.target = target; p.dice_coef = dice_coef; p.w_ce = w_ce; p.dloss = dloss; p.dlogits = dlogits;
+  p.loss_partials = loss_partials; p.wsum = wsum;
+  p.vec_out = ((uintptr_t)dlogits & 15) == 0;
+  seg_weights(p, class_weight, pixel_weight, has_ignore, ignore_index);
+  const int grid = oct_seg_loss_blocks(p.npix, d->classes);
+  hipStream_t s = as_stream(stream);
+  SEG_DISPATCH(seg_bwd_kernel, true, d, layout, grid, s, p);
+  return oct_check_launch("seg_loss_bwd_weighted");
+}
+
+extern "C" int oct_seg_loss_finalize_weighted(const OctHeadDesc* d, const double* loss_partials, int nblocks, float w_ce,
+                                              float w_dice, float dice_eps, float* loss_out, float* dice_coef, double* wsum_out,
+                                              void* stream) {
+  int rc = seg_check(d, OCT_SEG_NHWC, "oct_seg_loss_finalize_weighted");
+  if (rc) return rc;
+  OCT_CHECK(loss_partials && loss_out && dice_coef, "oct_seg_loss_finalize_weighted: null pointer (rows, loss_out, dice_coef)");
+  OCT_CHECK(nblocks > 0, "oct_seg_loss_finalize_weighted: bad row count %d", nblocks);
+  hipLaunchKernelGGL(seg_finalize_weighted_kernel, dim3(1), dim3(1024), 0, as_stream(stream), loss_partials, nblocks,
+                     d->classes, w_ce, w_dice, dice_eps, loss_out, dice_coef, wsum_out);
+  return oct_check_launch("seg_loss_finalize_weighted");
 }

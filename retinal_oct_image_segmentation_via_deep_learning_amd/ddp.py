@@ -196,12 +196,21 @@ class DataParallelTrainer:
 
     Models without an engine (the logits networks of blocks.py, mgunet.py, relaynet.py: losses.SegLossMixin) run their
     backward through autograd, which has no stage boundaries to hook: their gradient leaves as ONE bucket after backward,
-    and use_graph is refused."""
+    and use_graph is refused.
+
+    class_weight / ignore_index (constants of the run) and step(..., pixel_weight=map of the local shard) select the
+    weighted loss of losses.cross_entropy_dice.  Each rank normalises by the sum of ITS OWN weights, and the gradients are
+    then averaged over ranks: the same as per-rank mean losses under stock DDP, and like those not the loss of the
+    global batch when the ranks' weight sums differ.  The weighted loss is not captured: use_graph=True refuses
+    class_weight / ignore_index at construction and a pixel_weight in step()."""
 
     def __init__(self, model, lr=0.01, momentum=0.9, weight_decay=0.0, w_ce=1.0, w_dice=0.0, use_graph=False,
-                 graph_warmup=2, bucket_cap_bytes=3 << 20, always_communicate=False):
+                 graph_warmup=2, bucket_cap_bytes=3 << 20, always_communicate=False, class_weight=None, ignore_index=None):
         from .optim import FusedSGD
         staged = hasattr(model, "_engine")
+        if use_graph and (class_weight is not None or ignore_index is not None):
+            raise NotImplementedError("use_graph=True captures the unweighted fused step only: class_weight / ignore_index "
+                                      "need use_graph=False")
         if use_graph and not staged:
             raise NotImplementedError(f"use_graph=True needs an engine network (UNet, BioUNet, UNet3D); {type(model).__name__} "
                                       "runs its backward through autograd, which is not captured in a graph")
@@ -213,6 +222,10 @@ class DataParallelTrainer:
         buckets = bucket_plan_for(model, self.opt.layout, bucket_cap_bytes) if staged and not use_graph else None
         self.reducer = GradAllReducer(self.opt.flat_g, self.world, buckets, always_communicate=always_communicate)
         self.w_ce, self.w_dice = w_ce, w_dice
+        if class_weight is not None and not torch.is_tensor(class_weight):
+            # converted once, here: the per-step call then passes a device tensor
+            class_weight = torch.tensor([float(v) for v in class_weight], dtype=torch.float32, device=self.opt.flat_p.device)
+        self.class_weight, self.ignore_index = class_weight, ignore_index
         self.use_graph, self.graph_warmup = use_graph, graph_warmup
         self.graph = None
         self.graph_error = None
@@ -232,7 +245,10 @@ class DataParallelTrainer:
         torch.cuda.current_stream().wait_stream(side)
         self.graph = g
 
-    def step(self, x, target):
+    def step(self, x, target, pixel_weight=None):
+        if self.use_graph and pixel_weight is not None:
+            raise NotImplementedError("use_graph=True captures the unweighted fused step only: a pixel_weight map needs "
+                                      "use_graph=False")
         if self.use_graph and self.graph is None and self.graph_error is None and self._eager_steps >= self.graph_warmup:
             try:
                 self._capture(x, target)
@@ -249,7 +265,9 @@ class DataParallelTrainer:
         else:
             hook = self.reducer if (self.reducer.active and not self.use_graph) else None
             self.reducer.begin_step()
-            loss = self.model.forward_backward(x, target, self.w_ce, self.w_dice, stage_hook=hook)
+            loss = self.model.forward_backward(x, target, self.w_ce, self.w_dice, stage_hook=hook,
+                                               class_weight=self.class_weight, pixel_weight=pixel_weight,
+                                               ignore_index=self.ignore_index)
             self._eager_steps += 1
         scale = self.reducer.finish()       # launches whatever backward did not, then joins the streams
         self.opt.step(grad_scale=scale)

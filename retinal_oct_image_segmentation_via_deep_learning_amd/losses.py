@@ -4,6 +4,12 @@ The loss is the fused UNet head's (oracle/ref_cpu.py::loss_head_fwd / loss_head_
 -log softmax[target], Dice = 1 - mean_c (2 I_c + eps) / (P_c + Y_c + eps), loss = w_ce CE + w_dice Dice.  The per-workgroup
 rows of the loss kernels are reduced by oct_head_loss_finalize, so both heads share one definition.
 
+With class_weight / pixel_weight / ignore_index (each optional; the oct_seg_loss_*_weighted kernels):
+  omega_i = [t_i != ignore_index] * class_weight[t_i] * pixel_weight[i],   CE = sum omega_i ce_i / sum omega_i
+(F.cross_entropy(weight=, ignore_index=) when there is no map), and the Dice sums run over the pixels that are not ignored.
+sum omega is reduced on the device and read there by the backward kernel: a weighted step synchronises as little as an
+unweighted one, and a CE-only step still reads the logits once.  With all three absent the unweighted kernels run, unchanged.
+
   cross_entropy_dice(logits, target, ...)  NCHW fp32 logits (any network's output) -> 0-d differentiable loss; with
                                            w_dice == 0 a drop-in for F.cross_entropy(logits, target)
   SegLossMixin                             forward_backward / loss / predict for the networks that return logits
@@ -53,6 +59,42 @@ def _target(target, n, h, w, device):
     return target.contiguous()
 
 
+def _options(class_weight, pixel_weight, ignore_index, n, h, w, classes, device):
+    """The three options of the weighted loss, checked against the logits' geometry before anything is launched: None when
+    all are absent (the unweighted kernels then run), else (class_weight | None, pixel_weight | None, has_ignore, ignore_index)
+    with the weights as contiguous fp32 tensors on `device`.  A sequence of floats is converted here, once per call: pass a
+    device tensor to convert it once per training run."""
+    if class_weight is None and pixel_weight is None and ignore_index is None:
+        return None
+    device = torch.device(device)
+    if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
+        raise TypeError(f"ignore_index must be an int or None, got {type(ignore_index).__name__} {ignore_index!r}")
+    if ignore_index is not None and not -2 ** 63 <= ignore_index < 2 ** 63:
+        raise ValueError(f"ignore_index {ignore_index} is not an int64")
+    if class_weight is not None:
+        if not torch.is_tensor(class_weight):
+            vals = [float(v) for v in class_weight]
+            if len(vals) != classes:
+                raise RuntimeError(f"class_weight must have {classes} entries (one per class), got {len(vals)}")
+            class_weight = torch.tensor(vals, dtype=torch.float32, device=device)
+        if class_weight.dtype != torch.float32:
+            raise RuntimeError(f"class_weight must be fp32, got {class_weight.dtype}")
+        if tuple(class_weight.shape) != (classes,):
+            raise RuntimeError(f"class_weight must have {classes} entries (one per class), got shape {tuple(class_weight.shape)}")
+        if class_weight.device != device:
+            raise RuntimeError(f"class_weight is on {class_weight.device}, logits on {device}")
+        class_weight = class_weight.detach().contiguous()
+    if pixel_weight is not None:
+        if not torch.is_tensor(pixel_weight) or pixel_weight.dtype != torch.float32:
+            raise RuntimeError(f"pixel_weight must be an fp32 tensor, got {getattr(pixel_weight, 'dtype', type(pixel_weight).__name__)}")
+        if tuple(pixel_weight.shape) != (n, h, w):
+            raise RuntimeError(f"pixel_weight must have shape {(n, h, w)}, got {tuple(pixel_weight.shape)}")
+        if pixel_weight.device != device:
+            raise RuntimeError(f"pixel_weight is on {pixel_weight.device}, logits on {device}")
+        pixel_weight = pixel_weight.detach().contiguous()
+    return class_weight, pixel_weight, int(ignore_index is not None), int(ignore_index or 0)
+
+
 class _Loss:
     """One launch plan: descriptor, partial rows, [loss, ce, dice] and the Dice backward coefficients."""
 
@@ -92,12 +134,62 @@ class _Loss:
                                               _stream()), "oct_seg_loss_backward")
         return dl
 
+    # ---- weighted forms: opt = _options(...) ------------------------------------------------------------------------------
+    def weight_sum(self, target, opt):
+        """sum omega as one device double, from the labels and the map alone"""
+        scratch = torch.empty(self.blocks + 1, dtype=torch.float64, device=self.dev)
+        cw, pw, has_ig, ig = opt
+        L.check(L.lib().oct_seg_loss_weight_sum(C.byref(self.desc), target.data_ptr(), L.ptr(cw), L.ptr(pw), has_ig, ig,
+                                                scratch.data_ptr(), scratch[self.blocks:].data_ptr(), _stream()),
+                "oct_seg_loss_weight_sum")
+        return scratch[self.blocks:]
 
-def loss_and_dlogits(logits_nhwc, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7):
-    """Training head on NHWC logits: ([loss, ce, dice], dlogits).  Without a Dice term the backward pass also writes the CE
-    rows (the logits are read once; the Dice entry is then 0); with one, forward rows -> finalize -> backward."""
-    h = _Loss(logits_nhwc, L.SEG_NHWC)
+    def forward_weighted(self, target, opt):
+        part = self.partials()
+        cw, pw, has_ig, ig = opt
+        L.check(L.lib().oct_seg_loss_forward_weighted(C.byref(self.desc), self.layout, self.logits.data_ptr(), target.data_ptr(),
+                                                      L.ptr(cw), L.ptr(pw), has_ig, ig, part.data_ptr(), _stream()),
+                "oct_seg_loss_forward_weighted")
+        return part
+
+    def finalize_weighted(self, part, w_ce, w_dice, dice_eps):
+        """[loss, ce, dice], dice_coef and sum omega (device double) of weighted rows"""
+        out = torch.empty(3, dtype=torch.float32, device=self.dev)
+        coef = torch.empty(2 * L.MAX_CLASSES, dtype=torch.float32, device=self.dev)
+        wsum = torch.empty(1, dtype=torch.float64, device=self.dev)
+        L.check(L.lib().oct_seg_loss_finalize_weighted(C.byref(self.desc), part.data_ptr(), self.blocks, float(w_ce),
+                                                       float(w_dice), float(dice_eps), out.data_ptr(), coef.data_ptr(),
+                                                       wsum.data_ptr(), _stream()), "oct_seg_loss_finalize_weighted")
+        return out, coef, wsum
+
+    def backward_weighted(self, target, opt, wsum, dice_coef, w_ce, dloss=None, part=None):
+        dl = torch.empty_like(self.logits)
+        cw, pw, has_ig, ig = opt
+        L.check(L.lib().oct_seg_loss_backward_weighted(C.byref(self.desc), self.layout, self.logits.data_ptr(), target.data_ptr(),
+                                                       L.ptr(cw), L.ptr(pw), has_ig, ig, wsum.data_ptr(), L.ptr(dice_coef),
+                                                       float(w_ce), L.ptr(dloss), dl.data_ptr(), L.ptr(part), _stream()),
+                "oct_seg_loss_backward_weighted")
+        return dl
+
+
+def loss_and_dlogits(logits, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7, class_weight=None, pixel_weight=None,
+                     ignore_index=None, layout=L.SEG_NHWC):
+    """Training head on NHWC logits (or NCHW fp32 ones with layout=SEG_NCHW): ([loss, ce, dice], dlogits).  Without a Dice
+    term the backward pass also writes the CE rows (the logits are read once; the Dice entry is then 0); with one, forward
+    rows -> finalize -> backward.  With class_weight / pixel_weight / ignore_index the same two schedules on the weighted
+    kernels: sum omega comes from a pass over the labels and the map (CE only) or out of the forward rows (with Dice)."""
+    h = _Loss(logits, layout)
     t = _target(target, h.n, h.h, h.w, h.dev)
+    opt = _options(class_weight, pixel_weight, ignore_index, h.n, h.h, h.w, h.c, h.dev)
+    if opt is not None:
+        if w_dice == 0.0:
+            wsum = h.weight_sum(t, opt)
+            part = h.partials()
+            dl = h.backward_weighted(t, opt, wsum, None, w_ce, part=part)
+            return h.finalize_weighted(part, w_ce, w_dice, dice_eps)[0], dl
+        part = h.forward_weighted(t, opt)
+        out, coef, wsum = h.finalize_weighted(part, w_ce, w_dice, dice_eps)
+        return out, h.backward_weighted(t, opt, wsum, coef, w_ce)
     if w_dice == 0.0:
         part = h.partials()
         dl = h.backward(t, None, w_ce, part=part)
@@ -110,11 +202,16 @@ def loss_and_dlogits(logits_nhwc, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7):
 
 class _CrossEntropyDice(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, layout, w_ce, w_dice, dice_eps):
+    def forward(ctx, logits, target, layout, w_ce, w_dice, dice_eps, class_weight, pixel_weight, ignore_index):
         h = _Loss(logits.detach(), layout)
         t = _target(target, h.n, h.h, h.w, h.dev)
-        part, _ = h.forward(t)
-        out, coef = h.finalize(part, w_ce, w_dice, dice_eps)
+        ctx.opt = _options(class_weight, pixel_weight, ignore_index, h.n, h.h, h.w, h.c, h.dev)
+        ctx.wsum = None
+        if ctx.opt is not None:
+            out, coef, ctx.wsum = h.finalize_weighted(h.forward_weighted(t, ctx.opt), w_ce, w_dice, dice_eps)
+        else:
+            part, _ = h.forward(t)
+            out, coef = h.finalize(part, w_ce, w_dice, dice_eps)
         ctx.h, ctx.t, ctx.w_ce = h, t, w_ce
         ctx.coef = coef if w_dice != 0.0 else None
         return out[0]
@@ -123,16 +220,36 @@ class _CrossEntropyDice(torch.autograd.Function):
     def backward(ctx, dout):
         # the upstream gradient stays on the device: the kernel reads it, nothing synchronises
         g = dout.detach().to(torch.float32).contiguous()
-        dl = ctx.h.backward(ctx.t, ctx.coef, ctx.w_ce, dloss=g)
-        ctx.h = ctx.t = ctx.coef = None
-        return dl, None, None, None, None, None
+        if ctx.opt is not None:
+            dl = ctx.h.backward_weighted(ctx.t, ctx.opt, ctx.wsum, ctx.coef, ctx.w_ce, dloss=g)
+        else:
+            dl = ctx.h.backward(ctx.t, ctx.coef, ctx.w_ce, dloss=g)
+        ctx.h = ctx.t = ctx.coef = ctx.opt = ctx.wsum = None
+        return dl, None, None, None, None, None, None, None, None
 
 
-def cross_entropy_dice(logits, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7):
+def cross_entropy_dice(logits, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7, class_weight=None, pixel_weight=None,
+                       ignore_index=None):
     """w_ce * CE + w_dice * soft Dice of NCHW fp32 CUDA logits (B, C, H, W) against int64 labels (B, H, W): a 0-d loss
     that autograd differentiates through the HIP backward kernel.  w_dice == 0: F.cross_entropy(logits, target).
-    A label outside [0, C) gives a NaN loss (torch raises there); at most 16 classes."""
-    return _CrossEntropyDice.apply(logits, target, L.SEG_NCHW, float(w_ce), float(w_dice), float(dice_eps))
+    A label outside [0, C) gives a NaN loss (torch raises there); at most 16 classes.
+
+    class_weight: fp32 device tensor of C entries (or a sequence of floats, converted on every call); pixel_weight: fp32
+    device tensor (B, H, W), a constant of the loss -- no gradient is returned for it; ignore_index: int or None.  With
+    class_weight and ignore_index this is F.cross_entropy(logits, target, weight=class_weight, ignore_index=ignore_index);
+    a map multiplies each pixel's term and its share of the denominator.  ignore_index defaults to None, not torch's
+    -100: a label of -100 keeps giving NaN unless it is named here.  Everything ignored: NaN, as torch."""
+    return _CrossEntropyDice.apply(logits, target, L.SEG_NCHW, float(w_ce), float(w_dice), float(dice_eps), class_weight,
+                                   pixel_weight, ignore_index)
+
+
+def loss_only(h, target, w_ce, w_dice, dice_eps, opt):
+    """[loss, ce, dice] of a _Loss plan without a backward pass; opt: _options(...) or None"""
+    t = _target(target, h.n, h.h, h.w, h.dev)
+    if opt is not None:
+        return h.finalize_weighted(h.forward_weighted(t, opt), w_ce, w_dice, dice_eps)[0]
+    part, _ = h.forward(t)
+    return h.finalize(part, w_ce, w_dice, dice_eps)[0]
 
 
 class SegLossMixin:
@@ -149,19 +266,30 @@ class SegLossMixin:
         ops.flush_counters()      # what ToNCHW.forward does at the end of forward(): num_batches_tracked += 1
         return lg
 
-    def forward_backward(self, x, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7, stage_hook=None):
+    def _options_for(self, x, class_weight, pixel_weight, ignore_index):
+        """the weighted loss's options checked against the input's geometry, before the forward pass runs"""
+        if x.dim() != 4:
+            raise RuntimeError(f"expected a 4-D input, got {tuple(x.shape)}")
+        return _options(class_weight, pixel_weight, ignore_index, x.shape[0], x.shape[2], x.shape[3], self._classes(), x.device)
+
+    def forward_backward(self, x, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7, stage_hook=None, class_weight=None,
+                         pixel_weight=None, ignore_index=None):
         """Training step without the optimizer: forward to the NHWC logits, the loss kernels, backward.  OVERWRITES the
         `.grad` of every parameter that requires one (existing tensors stay the same objects -- FusedSGD's flat views --
         missing ones are allocated; a parameter the loss does not reach gets zeros) and returns the device tensor
         [loss, ce, dice]; with w_dice == 0 the Dice entry is 0.  stage_hook is accepted for the engine networks' signature
-        and ignored: there is one gradient bucket, which GradAllReducer.finish() sends after backward."""
+        and ignored: there is one gradient bucket, which GradAllReducer.finish() sends after backward.
+        class_weight / pixel_weight / ignore_index: the weighted loss of cross_entropy_dice, on the same NHWC logits."""
         if not self.training:
             raise RuntimeError("forward_backward needs train() mode (batch statistics)")
         _check_classes(self._classes())
+        opt = self._options_for(x, class_weight, pixel_weight, ignore_index)
+        if opt is not None:
+            class_weight, pixel_weight = opt[0], opt[1]
         params = [p for p in self.parameters() if p.requires_grad]
         with torch.enable_grad():
             lg = self._run_logits(x)
-        out, dl = loss_and_dlogits(lg, target, w_ce, w_dice, dice_eps)
+        out, dl = loss_and_dlogits(lg, target, w_ce, w_dice, dice_eps, class_weight, pixel_weight, ignore_index)
         # autograd.grad + one multi-tensor copy: zeroing .grad and letting backward accumulate into it costs one add launch
         # per parameter (~150 on AttU_Net)
         grads = torch.autograd.grad(lg, params, dl, allow_unused=True)
@@ -177,12 +305,12 @@ class SegLossMixin:
         return out
 
     @torch.no_grad()
-    def loss(self, x, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7):
+    def loss(self, x, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7, class_weight=None, pixel_weight=None, ignore_index=None):
         """[loss, ce, dice] of the current mode's forward pass (no gradients; buffers move as in model(x))."""
         _check_classes(self._classes())
+        opt = self._options_for(x, class_weight, pixel_weight, ignore_index)
         h = _Loss(self._run_logits(x), L.SEG_NHWC)
-        part, _ = h.forward(_target(target, h.n, h.h, h.w, h.dev))
-        return h.finalize(part, w_ce, w_dice, dice_eps)[0]
+        return loss_only(h, target, w_ce, w_dice, dice_eps, opt)
 
     @torch.no_grad()
     def predict(self, x):

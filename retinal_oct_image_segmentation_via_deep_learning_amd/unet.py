@@ -101,8 +101,24 @@ class _EngineNet(nn.Module):
         return self._run(x, train=self.training)
 
     # ---- fused extras (not in the reference) --------------------------------------
+    _weighted_loss = True   # False: the network refuses class_weight / pixel_weight / ignore_index (UNet3D)
+
+    def _loss_options(self, x, class_weight, pixel_weight, ignore_index):
+        """losses._options for this network's logits, checked before anything is launched; None: the fused head runs"""
+        if class_weight is None and pixel_weight is None and ignore_index is None:
+            return None
+        if not self._weighted_loss:
+            raise NotImplementedError(f"{type(self).__name__}: class_weight / pixel_weight / ignore_index are implemented for "
+                                      "the 2-D networks only; the volumetric loss head is the unweighted fused one")
+        from .losses import _check_classes, _options
+        if x.dim() != 4:
+            raise RuntimeError(f"expected a 4-D input, got {tuple(x.shape)}")
+        _check_classes(self._engine.ncls)
+        return _options(class_weight, pixel_weight, ignore_index, x.shape[0], x.shape[2], x.shape[3], self._engine.ncls, x.device)
+
     @torch.no_grad()
-    def forward_backward(self, x, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7, want_probs=False, stage_hook=None):
+    def forward_backward(self, x, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7, want_probs=False, stage_hook=None,
+                         class_weight=None, pixel_weight=None, ignore_index=None):
         """Training step without the optimizer: forward, fused CE(+Dice) loss head, full backward.
         Writes `.grad` of every parameter and returns the device tensor [loss, ce, dice]
         (plus the probabilities when want_probs).  With w_dice == 0 (and the fused head: 32 head
@@ -110,10 +126,28 @@ class _EngineNet(nn.Module):
         third entry is 0: the cross-entropy then comes out of the backward head pass and the forward
         one is skipped.  stage_hook: see UNetEngine.backward (data-parallel gradient buckets).
         A target outside [0, classes) -- where torch's nll_loss raises -- yields a NaN loss (device-side
-        flag, no synchronisation)."""
+        flag, no synchronisation).
+        class_weight / pixel_weight / ignore_index (losses.cross_entropy_dice defines them; each optional): the step
+        then leaves the fused head -- the forward writes NCHW fp32 logits, the weighted loss kernels of
+        csrc/seg_loss.hip give the loss and d(loss)/d(logits), and the backward starts from those through the
+        generic 1x1 head kernels.  The loss is on the logits also where forward() returns probabilities (UNet)."""
         if not self.training:
             raise RuntimeError("forward_backward needs train() mode (batch statistics)")
+        opt = self._loss_options(x, class_weight, pixel_weight, ignore_index)
         P = self._tensors()
+        if opt is not None:
+            from . import _lib
+            from .losses import loss_and_dlogits
+            ectx, probs, _, lg = self._engine.forward(P, x, train=True, want_probs=want_probs, want_logits=True)
+            out, dl = loss_and_dlogits(lg, target.to(device=lg.device, dtype=torch.int64), w_ce, w_dice, dice_eps, opt[0], opt[1],
+                                       ignore_index, layout=_lib.SEG_NCHW)
+            G = {}
+            for n, p in self.named_parameters():
+                if p.grad is None:
+                    p.grad = torch.empty_like(p.data)
+                G[n] = p.grad
+            self._engine.backward(P, ectx, G, dlogits=dl, stage_hook=stage_hook)
+            return (out, probs) if want_probs else out
         ectx, probs, _, _ = self._engine.forward(P, x, train=True, target=target,
                                                  loss_cfg=(w_ce, w_dice, dice_eps), want_probs=want_probs,
                                                  defer_loss=True)
@@ -126,8 +160,14 @@ class _EngineNet(nn.Module):
         return (ectx.loss, probs) if want_probs else ectx.loss
 
     @torch.no_grad()
-    def loss(self, x, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7):
+    def loss(self, x, target, w_ce=1.0, w_dice=0.0, dice_eps=1e-7, class_weight=None, pixel_weight=None, ignore_index=None):
         """[loss, ce, dice] of the current mode's forward pass (no gradients)."""
+        opt = self._loss_options(x, class_weight, pixel_weight, ignore_index)
+        if opt is not None:
+            from . import _lib
+            from .losses import _Loss, loss_only
+            _, _, _, lg = self._engine.forward(self._tensors(), x, train=self.training, want_probs=False, want_logits=True)
+            return loss_only(_Loss(lg, _lib.SEG_NCHW), target.to(device=lg.device, dtype=torch.int64), w_ce, w_dice, dice_eps, opt)
         ectx, _, _, _ = self._engine.forward(self._tensors(), x, train=self.training, target=target,
                                              loss_cfg=(w_ce, w_dice, dice_eps), want_probs=False)
         return ectx.loss

@@ -28,6 +28,8 @@ def _block3d(cin: int, cout: int, name: str) -> nn.Sequential:
 
 
 class UNet3D(_EngineNet):
+    _weighted_loss = False   # forward_backward / loss raise NotImplementedError for class_weight / pixel_weight / ignore_index
+
     def __init__(self, in_channels=1, out_channels=2, init_features=32, compute_dtype="bf16"):
         super().__init__()
         f = init_features

@@ -6,8 +6,14 @@
     torch  -- F.cross_entropy(model(x), t) + torch.optim.SGD: NCHW fp32 logits, ATen log_softmax / nll_loss
     fused  -- model.forward_backward(x, t) + FusedSGD: the loss kernels on the NHWC logits (losses.py, csrc/seg_loss.hip)
 
-usage: cfg_bench.py [steps] [rounds]     CFG_ONLY=1 / 4 / relaynet / mgunet2 runs one group.
-CFG_PROFILE=1: only the fused cfg4 step, 3 warm-up steps + 1 (for a rocprofv3 --kernel-trace --stats pass)."""
+usage: cfg_bench.py [steps] [rounds]     CFG_ONLY=1 / 4 / relaynet / mgunet2 / unet runs one group.
+CFG_PROFILE=1: only the fused cfg4 step, 3 warm-up steps + 1 (for a rocprofv3 --kernel-trace --stats pass).
+CFG_WEIGHTED=1: the weighted loss in the cfg4 pairs and the profile step -- class weights w (uniform in [0.25, 4]) and
+  ignore_index k = 255 on 20 % of the labels:
+    torch  -- F.cross_entropy(model(x), t, weight=w, ignore_index=k) + torch.optim.SGD
+    fused  -- model.forward_backward(x, t, class_weight=w, ignore_index=k) + FusedSGD (oct_seg_loss_*_weighted)
+  and, as group "unet" (only when named: CFG_ONLY=unet), UNet(1,8) at the headline shape 32x512x1024: the weighted step, which
+  leaves the fused head, against the unweighted fused-head step of the same build, alternating."""
 import os
 import statistics
 import sys
@@ -20,28 +26,40 @@ from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Lesions_Segment.
 from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Layers_Segment.BioNet_2020 import UNet as BioUNet  # noqa: E402
 from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Layers_Segment.MGUNet_2021 import MGUNet_2  # noqa: E402
 from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Layers_Segment.SD_Layer_Net.unet import AttU_Net  # noqa: E402
+from retinal_oct_image_segmentation_via_deep_learning_amd.SOTAS.Lesions_Segment.YNet_2022 import UNet  # noqa: E402
 from retinal_oct_image_segmentation_via_deep_learning_amd.optim import FusedSGD  # noqa: E402
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 WARMUP = 8     # the autograd-driven networks reach their steady state after ~8 steps (bench.py)
+WEIGHTED = bool(os.environ.get("CFG_WEIGHTED"))
+IGNORE = 255
 g = torch.Generator().manual_seed(1234)
 
 
-def stepper(model, x, t, fused):
+def weighted_options(t, ncls):
+    """(labels with 20 % set to IGNORE, class weights on the device); the generator advances only in weighted mode"""
+    w = (0.25 + 3.75 * torch.rand(ncls, generator=g)).cuda()
+    t = torch.where(torch.rand(t.shape, generator=g).cuda() < 0.2, torch.full_like(t, IGNORE), t)
+    return t, w
+
+
+def stepper(model, x, t, fused, w=None, k=None):
     model.cuda().train()
+    kw = {} if w is None else dict(class_weight=w, ignore_index=k)
     if fused:
         opt = FusedSGD(list(model.named_parameters()), lr=0.01, momentum=0.9)
 
         def step():
-            model.forward_backward(x, t)
+            model.forward_backward(x, t, **kw)
             opt.step()
     else:
         opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9)
+        tkw = {} if w is None else dict(weight=w, ignore_index=k)
 
         def step():
             opt.zero_grad(set_to_none=True)
-            F.cross_entropy(model(x), t).backward()
+            F.cross_entropy(model(x), t, **tkw).backward()
             opt.step()
     return step
 
@@ -65,12 +83,12 @@ def run(name, model, x, t):
           f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
 
 
-def pair(name, make, x, t):
+def pair(name, make, x, t, w=None, k=None):
     """the torch-CE path and the fused path of two identically seeded models, timed in alternating rounds"""
     torch.manual_seed(0)
-    st_torch = stepper(make(), x, t, False)
+    st_torch = stepper(make(), x, t, False, w, k)
     torch.manual_seed(0)
-    st_fused = stepper(make(), x, t, True)
+    st_fused = stepper(make(), x, t, True, w, k)
     for _ in range(WARMUP):
         st_torch()
         st_fused()
@@ -79,7 +97,8 @@ def pair(name, make, x, t):
         ms["torch"].append(timed(st_torch, steps) * 1e3)
         ms["fused"].append(timed(st_fused, steps) * 1e3)
     a, b = statistics.median(ms["torch"]), statistics.median(ms["fused"])
-    print(f"{name}: torch CE + SGD {a:.2f} ms/step, forward_backward + FusedSGD {b:.2f} ms/step "
+    tag = "weighted " if w is not None else ""
+    print(f"{name}: torch {tag}CE + SGD {a:.2f} ms/step, {tag}forward_backward + FusedSGD {b:.2f} ms/step "
           f"({a - b:+.2f} ms, {a / b:.3f}x; medians of {rounds} rounds x {steps} steps; "
           f"rounds torch {['%.2f' % v for v in ms['torch']]} fused {['%.2f' % v for v in ms['fused']]})", flush=True)
 
@@ -89,12 +108,37 @@ torch.manual_seed(0)
 if os.environ.get("CFG_PROFILE"):
     x = torch.randn(16, 1, 496, 768, generator=g).cuda()
     t = torch.randint(0, 3, (16, 496, 768), generator=g).cuda()
+    w = None
+    if WEIGHTED:
+        t, w = weighted_options(t, 3)
     torch.manual_seed(0)
-    step = stepper(AttU_Net(1, 3), x, t, True)
+    step = stepper(AttU_Net(1, 3), x, t, True, w, IGNORE if WEIGHTED else None)
     for _ in range(4):
         step()
     torch.cuda.synchronize()
-    print("cfg4 fused: 4 steps done")
+    print(f"cfg4 fused{' weighted' if WEIGHTED else ''}: 4 steps done")
+    sys.exit(0)
+if ONLY == "unet":
+    # the weighted step of an engine network (NCHW fp32 logits, the loss kernels, the generic 1x1 head backward) against the
+    # fused-head step it leaves, same model, same labels apart from the ignored ones
+    x = torch.randn(32, 1, 512, 1024, generator=g).cuda()
+    t = torch.randint(0, 8, (32, 512, 1024), generator=g).cuda()
+    tw, w = weighted_options(t, 8)
+    torch.manual_seed(0)
+    st_plain = stepper(UNet(1, 8), x, t, True)
+    torch.manual_seed(0)
+    st_w = stepper(UNet(1, 8), x, tw, True, w, IGNORE)
+    for _ in range(3):
+        st_plain()
+        st_w()
+    ms = {"plain": [], "weighted": []}
+    for _ in range(rounds):
+        ms["plain"].append(timed(st_plain, steps) * 1e3)
+        ms["weighted"].append(timed(st_w, steps) * 1e3)
+    a, b = statistics.median(ms["plain"]), statistics.median(ms["weighted"])
+    print(f"UNet(1,8) 32x512x1024: fused head {a:.2f} ms/step, weighted loss {b:.2f} ms/step ({b - a:+.2f} ms, {b / a:.3f}x; "
+          f"medians of {rounds} rounds x {steps} steps; rounds fused head {['%.2f' % v for v in ms['plain']]} "
+          f"weighted {['%.2f' % v for v in ms['weighted']]})", flush=True)
     sys.exit(0)
 if ONLY in ("", "1"):
     x = torch.randn(4, 1, 256, 256, generator=g).cuda(); t = torch.randint(0, 2, (4, 256, 256), generator=g).cuda()
@@ -107,5 +151,8 @@ for key, name, make, ncls in (("4", "cfg4 AttU_Net(1,3) 16x496x768", lambda: Att
     if ONLY in ("", key):
         x = torch.randn(16, 1, 496, 768, generator=g).cuda()
         t = torch.randint(0, ncls, (16, 496, 768), generator=g).cuda()
-        pair(name, make, x, t)
+        if WEIGHTED:
+            pair(name, make, x, *weighted_options(t, ncls), IGNORE)
+        else:
+            pair(name, make, x, t)
         torch.cuda.empty_cache()
