@@ -225,7 +225,8 @@ int oct_bn_eval_coeffs(int c, const float* gamma, const float* beta, const float
                        const float* running_var, float eps, float* scale, float* shift,
                        const float* conv_bias, void* stream);
 
-/* a = relu(y*scale+shift); p = maxpool2x2(a)  (nn.MaxPool2d(2,2), YNet_2022.py:516-522) */
+/* a = relu(y*scale+shift); p = maxpool2x2(a)  (nn.MaxPool2d(2,2), YNet_2022.py:516-522).  NaN follows torch: relu keeps it
+ * and a window that holds one pools to NaN (also a NaN scale / shift).                              */
 int oct_bn_relu_pool_fwd(int dtype, const void* y, const float* scale, const float* shift,
                          void* pooled, int n, int h, int w, int c, void* stream);
 /* a = relu(y*scale+shift) materialised (not used on the training path; for tests / export) */

@@ -24,7 +24,7 @@ static inline int bk_blocks(size_t work) {
   } while (0)
 
 __device__ __forceinline__ float act_apply(float z, int act) {
-  if (act == OCT_ACT_RELU) return fmaxf(z, 0.f);
+  if (act == OCT_ACT_RELU) return !(z <= 0.f) ? z : 0.f;   // keeps NaN like torch's relu (fmaxf(NaN, 0) is 0)
   if (act == OCT_ACT_SIGMOID) return 1.f / (1.f + __expf(-z));
   return z;
 }

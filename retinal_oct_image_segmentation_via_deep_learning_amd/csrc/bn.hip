@@ -123,7 +123,11 @@ __global__ void bn_relu_pool_fwd_kernel(const T* __restrict__ y, const float* __
       float v[V];
       ldv<T, V>(y + pix * c + g * V, v);
 #pragma unroll
-      for (int j = 0; j < V; ++j) m[j] = fmaxf(m[j], fmaf(v[j], sc[j], sh[j]));
+      for (int j = 0; j < V; ++j) {
+        // torch's rule (relu keeps NaN, a NaN candidate wins the window and then stays): fmaxf dropped it
+        const float z = fmaf(v[j], sc[j], sh[j]);
+        if (z > m[j] || __builtin_isnan(z)) m[j] = z;
+      }
     }
     store_vec<T, V>(out + (((size_t)img * ho + yo) * wo + xo) * c + g * V, m);
   }
@@ -156,7 +160,10 @@ __global__ void bn_relu_fwd_kernel(const T* __restrict__ y, const float* __restr
     ldv<float, V>(scale + g * V, sc); ldv<float, V>(shift + g * V, sh);
     ldv<T, V>(y + pix * c + g * V, v);
 #pragma unroll
-    for (int j = 0; j < V; ++j) v[j] = fmaxf(fmaf(v[j], sc[j], sh[j]), 0.f);
+    for (int j = 0; j < V; ++j) {
+      const float z = fmaf(v[j], sc[j], sh[j]);
+      v[j] = !(z <= 0.f) ? z : 0.f;   // relu that keeps NaN like torch's (fmaxf(NaN, 0) is 0)
+    }
     store_vec<T, V>(out + pix * c + g * V, v);
   }
 }

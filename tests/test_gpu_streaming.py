@@ -11,20 +11,17 @@ Every output lands in a buffer longer than the output, filled with NaN (or a sen
 counts run both vector widths (8 channels per thread when c % 8 == 0, else 1); one case per kernel and dtype has more
 than 2.5 * 2^20 work items (the grid is capped at 4096 x 256 = 2^20 threads) and a last pass that is not a multiple of 256.
 """
-import zlib
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import ref_stream as R
+from oracle.bounds import PAD, U, _LIVE, Out, one_rounding, reduced, same, seed, stored, ulp  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = ["f32", "bf16"]
 CH = [1, 3, 8, 24, 64, 512]
-PAD = 263                       # tail elements past every output
-U = 2.0 ** -24
 N_, H_, W_ = 2, 7, 11           # odd / prime spatial sizes
 BIG = (2, 1031, 1283)           # n * h * w = 2,645,546 pixels: 2.52 * 2^20, 42 past a multiple of 256
 
@@ -34,11 +31,6 @@ def L():
     from retinal_oct_image_segmentation_via_deep_learning_amd import _lib
     _lib.lib()
     return _lib
-
-
-def seed(*a):
-    """a seed that does not depend on the interpreter's string hashing"""
-    return zlib.crc32(repr(a).encode())
 
 
 def tdt(dt):
@@ -53,17 +45,7 @@ def st():
     return torch.cuda.current_stream().cuda_stream
 
 
-def stored(a, dt):
-    """float64 values as the storage type holds them (one rounding from fp32; fp32 from float64 is one rounding too)"""
-    t = torch.from_numpy(np.asarray(a, np.float64).astype(np.float32))
-    return t.double().numpy() if dt == "f32" else t.to(torch.bfloat16).double().numpy()
-
-
-# device inputs live until the test ends: a tensor made inline for a data_ptr() would otherwise go back to the caching
-# allocator before the kernel that reads it has run, and the next upload could land in its memory
-_LIVE = []
-
-
+# device inputs live until the test ends (see oracle/bounds.py)
 @pytest.fixture(autouse=True)
 def _keep_inputs_alive():
     yield
@@ -81,68 +63,6 @@ def f32dev(a):
     t = torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32))).cuda()
     _LIVE.append(t)
     return t
-
-
-class Out:
-    """an output tensor inside a longer NaN-filled (or sentinel-filled) buffer"""
-
-    def __init__(self, shape, dtype, fill=float("nan")):
-        self.numel = int(np.prod(shape))
-        self.buf = torch.full((self.numel + PAD,), fill, dtype=dtype, device="cuda")
-        self.fill = fill
-        self.t = self.buf[:self.numel].view(*shape)
-
-    def ptr(self):
-        return self.buf.data_ptr()
-
-    def host(self):
-        torch.cuda.synchronize()
-        tail = self.buf[self.numel:]
-        ok = torch.isnan(tail).all() if isinstance(self.fill, float) and np.isnan(self.fill) else (tail == self.fill).all()
-        assert bool(ok), "the kernel wrote past the end of its output"
-        return self.t.double().cpu().numpy() if self.t.is_floating_point() else self.t.cpu().numpy()
-
-
-def ulp(v, dt):
-    sp = np.spacing(np.abs(np.asarray(v, np.float64)).astype(np.float32)).astype(np.float64)
-    return sp * 65536.0 if dt == "bf16" else sp
-
-
-def same(got, ref, what):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    bad = ~((got == ref) | (np.isnan(got) & np.isnan(ref)))
-    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.size} differ, first at {np.unravel_index(bad.argmax(), bad.shape)}: "
-                           f"got {got[bad][0]!r} want {ref[bad][0]!r}")
-
-
-def one_rounding(got, ref64, terms, dt, what):
-    r = stored(ref64, dt)
-    got = np.asarray(got, np.float64)
-    assert got.shape == r.shape and np.isfinite(got).all(), what
-    err = np.abs(got - r)
-    cancel = 4 * U * np.asarray(terms, np.float64)
-    if dt == "bf16":
-        tol = ulp(r, dt) + cancel
-        # (a fp32 evaluation can cross a bf16 rounding boundary: one such element is allowed in a small tensor)
-        differ = int((got != r).sum())
-        assert differ <= max(1, 0.001 * got.size), f"{what}: {differ} of {got.size} elements differ from the once-rounded reference"
-    else:
-        tol = np.maximum(4 * ulp(r, dt), cancel)
-    bad = err > tol
-    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.size} outside the bound, first at {np.unravel_index(bad.argmax(), bad.shape)}: "
-                           f"got {got[bad][0]!r} want {r[bad][0]!r} (tol {tol[bad][0]:.3e})")
-
-
-def reduced(got, ref64, terms, count, dt, what, stored_dt=None):
-    """|got - ref| <= n 2^-24 sum|terms| (n = terms per output) + 1 ulp of the storage rounding"""
-    got, ref64 = np.asarray(got, np.float64), np.asarray(ref64, np.float64)
-    assert got.shape == ref64.shape and np.isfinite(got).all(), what
-    tol = np.asarray(count, np.float64) * U * np.asarray(terms, np.float64) + (ulp(ref64, stored_dt) if stored_dt else 0.0)
-    err = np.abs(got - ref64)
-    bad = err > tol
-    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.size} outside the bound, first at {np.unravel_index(bad.argmax(), bad.shape)}: "
-                           f"got {got[bad][0]!r} want {ref64[bad][0]!r} (tol {np.broadcast_to(tol, err.shape)[bad][0]:.3e})")
 
 
 def shapes(big_c=8):
@@ -192,6 +112,47 @@ def test_affine_act_fwd_without_residual_entry_point(L):
                                        L.ACT_RELU, out.ptr(), n * h * w, c, st()))
     ref, terms, _ = R.affine_act(y, sc, sh, R.ACT_RELU)
     one_rounding(out.host(), ref, terms, "bf16", "affine_act_fwd")
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("c", [1, 3, 8, 24, 64])
+@pytest.mark.parametrize("entry", ["act", "res", "res_shift"])
+def test_affine_relu_keeps_nan(L, dt, c, entry):
+    """torch.relu(NaN) is NaN: the output is NaN exactly where relu(y*scale + shift (+ res)) in float64 is, also through a NaN
+    scale; elsewhere nothing changes"""
+    n, h, w = N_, H_, W_
+    shape = (n, h, w, c)
+    rng = np.random.default_rng(seed("nan", c, entry, dt))
+    y = stored(rng.standard_normal(shape) * 3, dt)
+    y[0, 0, 0, 0] = y[0, 3, 4, min(7, c - 1)] = y[-1, h - 1, w - 1, c - 1] = y[-1, 2, 2, (c // 2 // 8) * 8] = np.nan
+    sc = (rng.uniform(0.5, 1.5, c) * rng.choice([-1, 1], c)).astype(np.float32)
+    sh = (rng.standard_normal(c) * 0.5).astype(np.float32)
+    res = stored(rng.standard_normal(shape), dt) if entry != "act" else None
+    rb = (rng.standard_normal(c) * 0.5).astype(np.float32) if entry == "res_shift" else None
+    if res is not None:
+        res[0, 1, 1, c - 1] = np.nan                              # a NaN residual reaches the output too
+    for nan_scale in ((False, True) if c > 1 else (False,)):
+        s = sc.copy()
+        if nan_scale:
+            s[c // 2] = np.nan
+        with np.errstate(invalid="ignore"):
+            z = y * s.astype(np.float64) + sh.astype(np.float64) + (0 if res is None else res + (0 if rb is None else rb.astype(np.float64)))
+        want = torch.relu(torch.from_numpy(z)).numpy()
+        assert np.isnan(want).sum() >= 3 and not np.isnan(want).all()
+        out = Out(shape, tdt(dt))
+        if entry == "act":
+            L.check(L.lib().oct_affine_act_fwd(dcode(L, dt), todev(y, dt).data_ptr(), f32dev(s).data_ptr(), f32dev(sh).data_ptr(), None,
+                                               L.ACT_RELU, out.ptr(), n * h * w, c, st()))
+        else:
+            L.check(L.lib().oct_affine_res_act_fwd(dcode(L, dt), todev(y, dt).data_ptr(), f32dev(s).data_ptr(), f32dev(sh).data_ptr(),
+                                                   todev(res, dt).data_ptr(), None if rb is None else f32dev(rb).data_ptr(),
+                                                   L.ACT_RELU, out.ptr(), n * h * w, c, st()))
+        got = out.host()
+        assert np.array_equal(np.isnan(got), np.isnan(want)), "NaN where torch.relu has NaN, nowhere else"
+        ok = ~np.isnan(want)
+        clean = lambda a: None if a is None else np.where(np.isnan(a), 0.0, a)          # noqa: E731
+        ref, terms, _ = R.affine_act(clean(y), np.where(np.isnan(s), 1.0, s), sh, R.ACT_RELU, clean(res), rb, store=lambda v: stored(v, dt))
+        one_rounding(np.where(ok, got, 0.0), np.where(ok, ref, 0.0), terms, dt, f"affine relu ({entry}) away from the NaNs")
 
 
 # act_bwd picks its vector width from the element count: 154 * c is a multiple of 8 only for c % 8 == 0 here
