@@ -421,6 +421,41 @@ int oct_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float
                  float weight_decay, float grad_scale, int first, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Optimizer layer over flat fp32 buffers (library 0.2.2, same OCT_VERSION): Adam / AdamW, the
+ * global gradient norm with its clip coefficient, SGD with a device-side gradient scale.
+ * Any n >= 1 and any 4-byte-aligned pointers; 16-byte-aligned buffers take the vector path, with
+ * the same bits.  No atomics and no synchronisation; the caller owns all memory.
+ *   dev_scale  (may be NULL): device pointer to ONE float that multiplies grad_scale -- out + 1 of
+ *              oct_grad_norm, so a clipped step needs no host round trip.
+ *   decay_mask (may be NULL): one byte per 64 floats, (n + 63) / 64 bytes; 0 = no weight decay for
+ *              the chunk (bit for bit the weight_decay = 0 result), anything else = decay.
+ * ------------------------------------------------------------------------------------------ */
+/* torch.optim.Adam (decoupled == 0) / AdamW (decoupled != 0), single tensor, no amsgrad:
+ *   g' = g * (grad_scale * *dev_scale);  Adam: g' += wd p;  AdamW: p *= 1 - lr wd
+ *   m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  p -= step_size * m / (sqrt(v) * inv_sqrt_bc2 + eps)
+ * step_size = lr / (1 - b1^t) and inv_sqrt_bc2 = 1 / sqrt(1 - b2^t) come from the host (float64,
+ * rounded once), as torch computes them; lr itself is read for the decoupled decay only.
+ * All-zero p, g, m, v give an update of exactly 0.  eps <= 0, betas outside [0, 1), negative lr /
+ * weight_decay / step_size and inv_sqrt_bc2 < 1 are OCT_E_INVALID.                              */
+int oct_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int decoupled, float step_size,
+                  float inv_sqrt_bc2, float grad_scale, const float* dev_scale,
+                  const uint8_t* decay_mask, void* stream);
+/* oct_sgd_step with dev_scale and decay_mask; both NULL: the same bits as oct_sgd_step */
+int oct_sgd_step_scaled(float* p, const float* g, float* buf, size_t n, float lr, float momentum,
+                        float weight_decay, float grad_scale, int first, const float* dev_scale,
+                        const uint8_t* decay_mask, void* stream);
+/* fp64 rows of `partials` that oct_grad_norm writes: a function of n alone (0 for n == 0) */
+int oct_grad_norm_blocks(size_t n);
+/* out[0] = || g * grad_scale ||_2, out[1] = min(1, max_norm / (out[0] + 1e-6)) as
+ * torch.nn.utils.clip_grad_norm_ (error_if_nonfinite = False: a NaN in g gives NaN, NaN; an Inf
+ * gives Inf, 0).  Two launches: fp64 sums of squares in a fixed order, one row per workgroup into
+ * partials [oct_grad_norm_blocks(n)], then one workgroup adds the rows in a fixed order.  Same
+ * bits on every call.  max_norm <= 0 is OCT_E_INVALID.                                          */
+int oct_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, double* partials,
+                  float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Building blocks of the reference's other U-Net families; NHWC tensors
  * of `dtype`, materialised activations.
  * ------------------------------------------------------------------------------------------ */

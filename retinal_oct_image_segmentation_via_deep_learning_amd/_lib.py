@@ -161,6 +161,12 @@ SIGNATURES = {
     "oct_nhwc_to_nchw": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "oct_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_int,
                              c_void_p]),
+    "oct_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_float,
+                              c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "oct_sgd_step_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_int,
+                                    c_void_p, c_void_p, c_void_p]),
+    "oct_grad_norm_blocks": (c_int, [c_size_t]),
+    "oct_grad_norm": (c_int, [c_void_p, c_size_t, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "oct_affine_act_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int,
                                    c_void_p]),
     "oct_affine_res_act_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
@@ -184,7 +190,7 @@ SIGNATURES = {
 
 _lib = None
 _lock = threading.Lock()
-# bumped whenever parameter memory is modified behind torch's back (FusedSGD, DDP broadcast)
+# bumped whenever parameter memory is modified behind torch's back (FusedSGD / FusedAdam, DDP broadcast)
 param_generation = [0]
 
 

@@ -184,7 +184,13 @@ def bucket_plan_for(model, layout, cap_bytes: int = 3 << 20):
 
 
 class DataParallelTrainer:
-    """model.forward_backward on the local shard (gradient buckets leave while backward runs) -> fused SGD.
+    """model.forward_backward on the local shard (gradient buckets leave while backward runs) -> fused optimizer step.
+
+    optimizer: "sgd" (optim.FusedSGD with lr / momentum / weight_decay, the default), "adam" or "adamw" (optim.FusedAdam /
+    FusedAdamW with lr / betas / eps / weight_decay; momentum is not read).  max_grad_norm clips the global norm of the
+    AVERAGED gradient: the norm kernel runs after the exchange has finished, with the step's own grad_scale = 1 / world.
+    no_decay(name, param) excludes parameters from weight decay (optim.NO_DECAY_1D).  state_dict() / load_state_dict() carry
+    the optimizer state and the eager-step count of the use_graph warm-up; the model's own state_dict is saved beside them.
 
     use_graph: the ~150 kernel launches of forward + loss + backward are recorded once into a HIP
     graph (torch.cuda.CUDAGraph, capture on the stream the C ABI launches on) and replayed per
@@ -205,8 +211,11 @@ class DataParallelTrainer:
     class_weight / ignore_index at construction and a pixel_weight in step()."""
 
     def __init__(self, model, lr=0.01, momentum=0.9, weight_decay=0.0, w_ce=1.0, w_dice=0.0, use_graph=False,
-                 graph_warmup=2, bucket_cap_bytes=3 << 20, always_communicate=False, class_weight=None, ignore_index=None):
-        from .optim import FusedSGD
+                 graph_warmup=2, bucket_cap_bytes=3 << 20, always_communicate=False, optimizer="sgd", betas=(0.9, 0.999),
+                 eps=1e-8, max_grad_norm=None, no_decay=None, class_weight=None, ignore_index=None):
+        from .optim import FusedAdam, FusedAdamW, FusedSGD
+        if optimizer not in ("sgd", "adam", "adamw"):
+            raise ValueError(f"optimizer={optimizer!r}: one of 'sgd', 'adam', 'adamw'")
         staged = hasattr(model, "_engine")
         if use_graph and (class_weight is not None or ignore_index is not None):
             raise NotImplementedError("use_graph=True captures the unweighted fused step only: class_weight / ignore_index "
@@ -215,7 +224,13 @@ class DataParallelTrainer:
             raise NotImplementedError(f"use_graph=True needs an engine network (UNet, BioUNet, UNet3D); {type(model).__name__} "
                                       "runs its backward through autograd, which is not captured in a graph")
         self.model = model
-        self.opt = FusedSGD(list(model.named_parameters()), lr=lr, momentum=momentum, weight_decay=weight_decay)
+        if optimizer == "sgd":
+            self.opt = FusedSGD(list(model.named_parameters()), lr=lr, momentum=momentum, weight_decay=weight_decay,
+                                max_grad_norm=max_grad_norm, no_decay=no_decay)
+        else:
+            cls = FusedAdam if optimizer == "adam" else FusedAdamW
+            self.opt = cls(list(model.named_parameters()), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                           max_grad_norm=max_grad_norm, no_decay=no_decay)
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         broadcast_parameters(self.opt.flat_p)
         broadcast_buffers(model)
@@ -272,6 +287,18 @@ class DataParallelTrainer:
         scale = self.reducer.finish()       # launches whatever backward did not, then joins the streams
         self.opt.step(grad_scale=scale)
         return loss
+
+    def state_dict(self) -> dict:
+        """Optimizer state (torch layout, optim.FusedSGD / FusedAdam.state_dict) and the number of eager steps taken."""
+        return {"optimizer": self.opt.state_dict(), "eager_steps": self._eager_steps}
+
+    def load_state_dict(self, sd: dict):
+        """Restores what state_dict() saved.  A captured graph is dropped: it is recorded again once the restored eager-step
+        count has reached graph_warmup."""
+        self.opt.load_state_dict(sd["optimizer"])
+        self._eager_steps = int(sd["eager_steps"])
+        self.graph = None
+        self.graph_error = None
 
     def global_metric_counts(self, sums):
         """Sum per-rank confusion counts [tp,t,p,tn,fp,fn] over ranks (48-byte all-reduce)."""
