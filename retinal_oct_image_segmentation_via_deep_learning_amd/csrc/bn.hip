@@ -518,9 +518,7 @@ __global__ void __launch_bounds__(EW_THREADS) bn_bwd_apply_prelu_flat_kernel(T* 
 }
 // 1 when the two entry points below take this channel count (else: oct_affine_prelu_bwd + the plain passes)
 extern "C" int oct_prelu_bn_fused_ok(int dtype, int c) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("OCT_PRELU_FUSED"); on = (e && e[0] == '0') ? 0 : 1; }
-  return (on && (dtype == OCT_DT_BF16 || dtype == OCT_DT_F32) && c > 0 && vec_width(c) == 8 && lane_mapping_ok(c, 8)) ? 1 : 0;
+  return ((dtype == OCT_DT_BF16 || dtype == OCT_DT_F32) && c > 0 && vec_width(c) == 8 && lane_mapping_ok(c, 8)) ? 1 : 0;
 }
 // partials: [oct_dact_bn_reduce_blocks(n, h, w, c, 0)][2][c]; dalpha: float[1], zeroed by the caller
 extern "C" int oct_dact_bn_reduce_prelu(int dtype, const void* da, const void* y, const float* scale, const float* shift,
@@ -560,9 +558,7 @@ static bool pool_coalesced_ok(int n, int h, int w, int c) {
 }
 // 1 when the pooled BatchNorm backward can run as reduce-only pass (oct_dact_bn_reduce with g = NULL) + oct_bn_bwd_apply_pool
 extern "C" int oct_bn_bwd_apply_pool_ok(int dtype, int n, int h, int w, int c) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("OCT_POOL_APPLY"); on = (e && e[0] == '0') ? 0 : 1; }
-  return (on && (dtype == OCT_DT_BF16 || dtype == OCT_DT_F32) && n > 0 && h > 1 && w > 1 && (h % 2) == 0 && (w % 2) == 0 &&
+  return ((dtype == OCT_DT_BF16 || dtype == OCT_DT_F32) && n > 0 && h > 1 && w > 1 && (h % 2) == 0 && (w % 2) == 0 &&
           pool_coalesced_ok(n, h, w, c)) ? 1 : 0;
 }
 // dy = k0*g + k1*y + k2 with g = [relu(bn(y)) > 0] * (da + dpool routed to the first maximum of its 2x2 window) re-derived

@@ -81,14 +81,9 @@ __global__ void __launch_bounds__(512) gemm1_kernel(const Gemm1Params p) {
   }
   // iterator of the stage being ISSUED (two ahead of the one being multiplied); clamps at the last stage.  Everything is a
   // counter chain: decoding (tile, block, chunk) with integer divisions cost the first version ~2 k cycles per stage.
-#ifndef G1_ROTATE
-#define G1_ROTATE 0   /* measured (r3, same box): no difference on any launch -- L2 hot-spotting of the lockstep weight reads is not what the chunk waits for */
-#endif
-  // ROTATE: workgroup b walks the K chunks of every item starting at chunk rot(b) (wrapping): without it all 256 workgroups
-  // ask the L2 for the SAME weight fragments at the same moment (they run in lockstep through identical items), and every
-  // byte has to be delivered 32 times per XCD through the few channels that hold it.  fp32 accumulation order changes with
-  // the workgroup (not from run to run); exact-arithmetic tests are order-independent by construction.
-  const int rot = G1_ROTATE ? (int)((blockIdx.x >> 3) % (unsigned)p.nch) : 0;
+  // every workgroup walks the K chunks of an item from chunk 0 (a per-workgroup starting chunk measured no difference and was
+  // removed); the start values keep their general form: folded by hand, hipcc orders two scalar moves differently
+  const int rot = 0;
   const int rot_dydx = S2D ? (rot * 64) / p.c0 : 0, rot_cc = S2D ? rot * 64 - rot_dydx * p.c0 : 0;
   struct It { int ch, pch, nb, txi, tyi, img, dydx, cc; };   // ch: chunks done in this item; pch: the physical chunk
   auto it_init = [&](int item) {

@@ -61,17 +61,8 @@ __device__ __forceinline__ float bf16hi(unsigned u) { return __uint_as_float(u &
 // D3: the depth taps / image maps of the volumetric network (OctConvDesc.depth, out_img_*).  A template switch, not a
 // runtime one: the same code guarded by `p.depth > 0` inside the producers' issue path cost the 2-D benchmark 12 % of
 // its igemm2 time (measured: 13.7 -> 15.4 ms per step), these kernels being bound by exactly that path.
-#ifndef IG2_M16
-#define IG2_M16 1
-#endif
-#ifndef IG2_M16_NF1
-#define IG2_M16_NF1 0
-#endif
-#ifndef IG2_PIXB16
-#define IG2_PIXB16 96
-#endif
 // which instantiations multiply with v_mfma_f32_16x16x32_bf16 (see M16 in the kernel)
-template <int TAPS, int NF, bool WRES> constexpr bool ig2_m16() { return IG2_M16 && TAPS != 1 && !WRES && (NF == 2 || IG2_M16_NF1); }
+template <int TAPS, int NF, bool WRES> constexpr bool ig2_m16() { return TAPS != 1 && !WRES && NF == 2; }
 // Pixel pitch of the LDS halo tile (bytes; 32 bf16 = 64 B of payload).  Register staging pads the pixel so that a wave's
 // ds_read_b128 of one fragment touches every bank once -- and which pad does that depends on the lane -> pixel map of the
 // MFMA shape (bank model of MI355X_MICROARCH.md, LDS: ds_read_b128 is serviced in four 16-lane groups):
@@ -79,7 +70,7 @@ template <int TAPS, int NF, bool WRES> constexpr bool ig2_m16() { return IG2_M16
 //   16x16x32 (lane = pixel l & 15, k quarter l >> 4):     96 B: 4 LDS cycles per read   (80 B: 8 -- the pitch round 2 ran the
 //                                                          16x16x32 kernels on: every activation read paid a 2-way conflict)
 // DMA tiles are dense (64 B) with the swizzle on the source address.  tools/lds_swizzle_check.py enumerates all of these.
-template <int TAPS, int NF, bool WRES, bool DMA> constexpr int ig2_pixb() { return DMA ? 64 : (ig2_m16<TAPS, NF, WRES>() ? IG2_PIXB16 : 80); }
+template <int TAPS, int NF, bool WRES, bool DMA> constexpr int ig2_pixb() { return DMA ? 64 : (ig2_m16<TAPS, NF, WRES>() ? 96 : 80); }
 
 // 16 zero bytes in device memory: the source of every LDS-DMA lane whose pixel is padding (a DMA cannot write a constant)
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4];
@@ -121,7 +112,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
   // Why: these kernels are power-bound and the chip holds a higher clock on this shape -- a timing-only
   // build that issued the same FLOPs as 16x16x32 measured -9 % on fprop / dgrad of the Cout >= 128 layers.
   constexpr bool M16 = ig2_m16<TAPS, NF, WRES>();   // NF == 1: 5-12 % slower with the deferred epilogue riding on the half-steps,
-                                                                                    // +0.06 ms per step with the un-deferred one (-DIG2_M16_NF1=1): stays on 32x32x16
+                                                                                    // +0.06 ms per step with the un-deferred one: stays on 32x32x16
   typedef Mma<bf16_t> M;
   typedef M::Frag Frag;
 
@@ -249,18 +240,13 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
       for (int i = 0; i < NSLOT; ++i) {
         const bool ok = (code[i] & edge) == 0;
         const unsigned char* src = ok ? hb + goff[i] : zsrc;
-#ifndef IG2_DMA_NT
-#define IG2_DMA_NT 0
-#endif
-        __builtin_amdgcn_global_load_lds((gl_void*)src, (lds_void*)(dst + i * 4096), 16, 0, IG2_DMA_NT ? 2 : 0);
-#ifndef IG2_DMA_SLEEP
-#define IG2_DMA_SLEEP 6
-#endif
+        __builtin_amdgcn_global_load_lds((gl_void*)src, (lds_void*)(dst + i * 4096), 16, 0, 0);
         // the producers have nothing else to do: pace the tile's requests over the stage instead of sending them as one burst
         // in front of the MFMA waves' weight loads (same reasoning as SPREAD below); s_sleep counts 64-cycle units
         // (the one-fragment kernels' stages are 2.3 k cycles: a third of the pause; same box, r3: -5...-7 % on the Cout >= 128
         //  launches with 6, +3 % on the 64-channel ones with 6, neutral with 2)
-        if (TAPS != 1 && IG2_DMA_SLEEP > 0 && i + 1 < NSLOT) __builtin_amdgcn_s_sleep(NF == 2 ? IG2_DMA_SLEEP : IG2_DMA_SLEEP / 3);
+        constexpr int DMA_SLEEP = 6;
+        if (TAPS != 1 && i + 1 < NSLOT) __builtin_amdgcn_s_sleep(NF == 2 ? DMA_SLEEP : DMA_SLEEP / 3);
       }
     };
     // all but the youngest NBUF - 2 stages have landed (vmcnt = simm16[15:14 | 3:0]); then the raw barrier
@@ -371,11 +357,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
     };
     auto issue_slot = [&](const IssueSt& st, int i, u32x4& r, unsigned& vm) {
       const bool ok = (!D3 || st.zok) && (code[i] & st.edge) == 0;
-#ifndef IG2_PNT
-#define IG2_PNT 0
-#endif
-      if (IG2_PNT) r = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(st.hb + (ok ? __umul24((unsigned)relp[i], st.cs2) : st.safe)));
-      else r = *reinterpret_cast<const u32x4*>(st.hb + (ok ? __umul24((unsigned)relp[i], st.cs2) : st.safe));
+      r = *reinterpret_cast<const u32x4*>(st.hb + (ok ? __umul24((unsigned)relp[i], st.cs2) : st.safe));
       vm |= ok ? (1u << i) : 0u;
     };
     auto issue = [&](u32x4 (&Rr)[NSLOT], unsigned& vm) {
@@ -384,7 +366,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
 #pragma unroll
       for (int i = 0; i < NSLOT; ++i) issue_slot(st, i, Rr[i], vm);
     };
-    struct CommitSt { float s[8], b[8]; float flo; unsigned flo_pk; bool xf; };
+    struct CommitSt { float s[8], b[8]; float flo; bool xf; };
     auto commit_begin = [&](bool always) -> CommitSt {
       CommitSt st;
       const int ch = c_ch;
@@ -397,7 +379,6 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
       const bool first = s2d || chc * 32 < p.c0;
       st.xf = first ? (p.xf0 != 0) : (p.xf1 != 0);
       st.flo = xf_floor(first ? p.xf0 : p.xf1);   // wave-uniform: 0 (BN + ReLU) or -inf (plain affine)
-      st.flo_pk = xf_floor_pk(first ? p.xf0 : p.xf1);
       if (st.xf || always) {
         const int kx = s2d ? p.c0 : p.c0 + p.c1;
         const f32x4 s0 = *reinterpret_cast<const f32x4*>(sxf + cg), s1 = *reinterpret_cast<const f32x4*>(sxf + cg + 4);
@@ -420,13 +401,9 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
         {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            if (OCT_PK_RELU) {
-              v[j] = pk_clamp_bf16(pack_bf16x2(fmaf(bf16lo(v[j]), st.s[2 * j], st.b[2 * j]), fmaf(bf16hi(v[j]), st.s[2 * j + 1], st.b[2 * j + 1])), st.flo_pk);
-            } else {
             const float lo = fmaxf(fmaf(bf16lo(v[j]), st.s[2 * j], st.b[2 * j]), st.flo);
             const float hi = fmaxf(fmaf(bf16hi(v[j]), st.s[2 * j + 1], st.b[2 * j + 1]), st.flo);
             v[j] = pack_bf16x2(lo, hi);
-            }
           }
         }
         // out-of-image pixels are exactly zero (padding applies to the activated tensor)
@@ -451,16 +428,13 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
     // branch-free (the stage count is padded to a multiple of D, both roles run the padded count,
     // indices clamp to the last stage): with branches around the loads hipcc protects the ring
     // registers with s_waitcnt vmcnt(0) and the prefetch collapses.
-#ifndef IG2_PSPREAD
-#define IG2_PSPREAD 1
-#endif
     // SPREAD (3x3 kernels whose sources are all transformed on load): slot i of the next stage is committed and IMMEDIATELY
     // re-issued for the stage after next, so the stage's global loads leave one by one over the ~3.7 k cycles of commit work
     // instead of as one burst behind it.  Why: the MFMA waves stream their weights from L2 through the same per-CU
     // load path, and while a burst of HBM-missing tile loads sat in it the weight loads' latency exceeded the ring's lead
     // (profiles/r03_ig2_traces.txt: stages that coincide with a new tile's loads ran 30-60 % longer).
     // (not the resident-weight kernels: their MFMA waves load nothing, and an HBM-bound kernel wants its requests out early)
-    const bool spread = IG2_PSPREAD && TAPS != 1 && !D3 && !WRES && p.xf0 != 0 && (p.c1 == 0 || p.xf1 != 0);
+    const bool spread = TAPS != 1 && !D3 && !WRES && p.xf0 != 0 && (p.c1 == 0 || p.xf1 != 0);
     if (spread) {
       for (int s0 = 0; s0 < nstage_pad; s0 += D) {
 #pragma unroll
@@ -506,10 +480,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
   // ================================= MFMA waves (4) =================================
   // each SIMD hosts one MFMA wave and one producer wave: the MFMA wave must win issue arbitration
   // against the partner's VALU-dense staging code (static priority, MI355X_MICROARCH.md item 4)
-#ifndef IG2_MFMA_PRIO
-#define IG2_MFMA_PRIO 3
-#endif
-  __builtin_amdgcn_s_setprio(IG2_MFMA_PRIO);
+  __builtin_amdgcn_s_setprio(3);
   const int r = lane & 31, hh = lane >> 5;
   const int wm = wave / WN, wn = wave % WN;
 
@@ -533,38 +504,20 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
       for (int q = 0; q < NF; ++q) asm volatile("" : "+v"(wres[s][q]));
   }
 
-#ifndef IG2_PF4
-#define IG2_PF4 9
-#endif
-#ifndef IG2_PF8
-#define IG2_PF8 3
-#endif
-  constexpr int PF = (KSTEPS == 2) ? 2 : ((MF * NF >= 8) ? ((KSTEPS % IG2_PF8 == 0) ? IG2_PF8 : 3) : ((MF * NF >= 4) ? (TAPS == 21 ? 7 : IG2_PF4) : 9));   // PF4: 6 until round 3 (42 steps: 7)
+  constexpr int PF4 = 9, PF8 = 3;   // ring depth with four / eight accumulator fragments per wave
+  constexpr int PF = (KSTEPS == 2) ? 2 : ((MF * NF >= 8) ? PF8 : ((MF * NF >= 4) ? (TAPS == 21 ? 7 : PF4) : 9));   // PF4: 6 until round 3 (42 steps: 7)
   static_assert(KSTEPS % PF == 0, "ring slots must line up across stages");
   Frag wring[(WRES || M16) ? 1 : PF][NF];
   // M16: weights of two taps.  Tap t sits in slot t & 1 and tap t + 1 is fetched while it multiplies; a stage has nine taps,
   // so the next stage's tap 0 lands in slot 1 and is moved to slot 0 when that stage starts (16 v_mov per stage; a third
   // slot instead cost 16 more registers and spilled the 128-channel kernels)
-#ifndef IG2_WRING3
-#define IG2_WRING3 1
-#endif
   // WR3: three weight slots, tap t in slot t % 3, tap t + 2 fetched while tap t multiplies (two taps = ~1000 matrix cycles
   // of lead; nine taps per stage, so the slots line up across stages and nothing has to be moved).  With two slots the
   // lead was ONE tap (~500 cycles), less than an L2 hit takes while the producers' loads of a new tile miss to HBM: the
   // stages that coincide with those loads ran 30-60 % longer (in-kernel timeline, profiles/r03_ig2_traces.txt: MFMA phase
   // 5.5 k cycles on even stages, 7.3-9.3 k on odd ones).
-#ifndef IG2_WR3_RAGGED
-#define IG2_WR3_RAGGED 0
-#endif
-  constexpr bool WR3 = IG2_WRING3 && M16 && (!RAGGED || IG2_WR3_RAGGED);   // (the ragged instantiations spill 6-10 dwords with the third slot)
-#ifndef IG2_WRING4
-#define IG2_WRING4 0
-#endif
-  // WR4: FOUR weight slots (tap t + 3 fetched while tap t multiplies: three taps = ~1.5 k matrix cycles of lead).  Nine taps do not
-  // line up with four slots: the next stage's taps 0-2 land in slots 1-3 and are moved down by one when that stage starts
-  // (48 v_mov per stage).  The 16 registers come from the activation fragments: a ring of six instead of two sets of four.
-  constexpr bool WR4 = IG2_WRING4 && WR3 && MF == 4;
-  constexpr int NWS = WR4 ? 4 : (WR3 ? 3 : 2);
+  constexpr bool WR3 = M16 && !RAGGED;   // (the ragged instantiations spill 6-10 dwords with the third slot)
+  constexpr int NWS = WR3 ? 3 : 2;
   Frag a16[M16 ? NWS : 1][M16 ? 2 * NF : 1];
   f32x16 acc[MF][NF];
   float s1[STATS ? NF : 1][16], s2[STATS ? NF : 1][16];  // BN partial sums (lane = pixel column)
@@ -668,34 +621,6 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
 #endif
     }
   };
-#ifndef IG2_PERM_EPI
-#define IG2_PERM_EPI 0   /* measured (r3, same box, two runs): +1...+6 % on every 16x16x32 launch -- 32-B store segments instead of 64-B ones */
-#endif
-  // 16x16x32 accumulators leave WITHOUT the LDS transpose: lane (r16, kg) holds, per channel half cc, channels 16cc + 4kg ..+3
-  // of pixel r16 (quarter half 0) and of pixel 16 + r16 (half 1) -- v_permlane16_swap trades the half-1 piece of the even kg
-  // rows for the half-0 piece of the odd ones, after which a lane owns 8 consecutive channels (16 B) of ONE pixel:
-  // pixel 16*(kg&1) + r16, channels 16cc + 8*(kg>>1).  Two 16-B stores per fragment, every pixel's 32 B written by two
-  // neighbouring lanes; no ds_write / ds_read / lgkmcnt round trips (the un-deferred eight-fragment epilogue through LDS was
-  // 4.7-5.0 k cycles per item with the matrix pipe idle: profiles/r03_ig2_traces.txt).
-  constexpr bool PERM_EPI = IG2_PERM_EPI && M16 && !DEFER;
-  auto frag_store_perm = [&](int m, int q, const unsigned (&pk)[8]) {
-    if (RAGGED && e_tyi * TH + wm * MF + m >= p.h) return;   // ragged last tile row (wave-uniform)
-    const int wlim = (RAGGED && (e_txi + 1) * TW > p.w) ? p.w - e_txi * TW : TW;
-    const int kg = lane >> 4, r16 = lane & 15;
-    const int px = 16 * (kg & 1) + r16;
-    unsigned char* const fb = e_fb[q] + (size_t)m * e_rowb[q];
-    const unsigned loff = __umul24((unsigned)px, e_pstep[q]) + (unsigned)(kg >> 1) * 16u;
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      // quarters S = cc (pixel half 0) and 2 + cc (pixel half 1): two dwords each
-      unsigned a0 = pk[2 * cc], a1 = pk[2 * cc + 1], b0 = pk[2 * (2 + cc)], b1 = pk[2 * (2 + cc) + 1];
-      auto r0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
-      auto r1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-      const u32x4 v = {r0[0], r1[0], r0[1], r1[1]};
-      if (RAGGED && px >= wlim) continue;   // ragged last tile column
-      *reinterpret_cast<u32x4*>(fb + (loff + (unsigned)cc * 32u)) = v;
-    }
-  };
   auto store_frag = [&](int m, int q) {   // fragment (m, q) of the item recorded by set_item, back to back
     u32x4 tv[2];
     frag_to_lds(packed[DEFER ? m : 0][DEFER ? q : 0]);
@@ -703,29 +628,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
     frag_store(m, q, tv);
   };
 
-#ifndef IG2_EARLYB
-#define IG2_EARLYB 0   /* measured (r3, same box, two runs each): 11.36 / 11.36 ms without, 11.42 / 11.34 ms with, over the 3x3 launches */
-#endif
-  // EARLYB (16x16x32 kernels, off): the activation fragments of a stage's FIRST half-step are read right behind the barrier that
-  // publishes the stage, before the ~240 instructions of per-stage set-up (statistics flush, accumulator clear, weight
-  // addresses) that precede them in program order.  The idea: the first MFMA of a stage waits an LDS round trip behind that
-  // set-up.  The in-kernel timeline (profiles/r03_ig2_timeline_late.txt) shows the stage IS bound by the MFMA waves (they wait
-  // ~100 cycles at the barrier, the producers ~2.9 k), but moving the reads changed no launch: the set-up is long enough to
-  // cover the round trip either way.
-  constexpr bool EARLYB = IG2_EARLYB && M16 && !(IG2_WRING4 && MF == 4 && !RAGGED);
-  Frag b16e[EARLYB ? MF : 1];
-  auto early_b = [&](int cur_) {
-    if constexpr (EARLYB) {
-      const int r16 = lane & 15, kg = lane >> 4;
-#pragma unroll
-      for (int m = 0; m < MF; ++m) {
-        if constexpr (DMA) b16e[m] = M::load(smem + (unsigned)(cur_ * BUFB + ((wm * MF + m) * LW + r16) * 64 + ((kg ^ ((r16 >> 1) & 3)) * 16)));
-        else b16e[m] = M::load(buf0 + cur_ * BUFB + ((wm * MF + m) * LW + r16) * PIXB + kg * 16);
-      }
-    }
-  };
   __syncthreads();  // stage 0 is in LDS
-  early_b(0);
   int cur = 0, pending_tile = -1, pending_nbi = 0, parity = 0;
   int item = 0, ch = 0;                                        // item = index within this workgroup's items
   int tile_c = t_first, nbi_c = nbi_first;                     // (tile, channel block) of `item`, kept as counters:
@@ -919,58 +822,13 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
 #pragma unroll
             for (int c = 0; c < 2 * NF; ++c) a16[1][c] = wfrag(false, c, 1);
           }
-          if constexpr (WR4) {
-#pragma unroll
-            for (int c = 0; c < 2 * NF; ++c) a16[2][c] = wfrag(false, c, 2);
-          }
-        } else if constexpr (WR4) {
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int c = 0; c < 2 * NF; ++c) a16[j][c] = a16[j + 1][c];   // taps 0-2 of this stage, fetched under the previous one's taps 6-8
         } else if constexpr (!WR3) {
 #pragma unroll
           for (int c = 0; c < 2 * NF; ++c) a16[0][c] = a16[1][c];   // fetched under the previous stage's last tap
         }
-        if constexpr (WR4) {
-          // activation fragments f = s * MF + m (72 per stage) through a ring of six: the read of fragment f + 5 is issued before
-          // the MFMAs of fragment f (320 matrix cycles of lead)
-          constexpr int RB = 6, NFRAG = KSTEPS * MF;
-          static_assert(NFRAG % RB == 0, "the fragment ring must line up across stages");
-          Frag bq[RB];
-#pragma unroll
-          for (int f = 0; f < RB - 1; ++f) bq[f] = M::load(bptr(f / MF, f % MF));
-#pragma unroll
-          for (int s = 0; s < KSTEPS; ++s) {
-            const int t = s >> 1;
-#ifndef ABL_NO_WLOAD
-            if ((s & 1) == 0) {   // weights of tap t + 3 (the next stage's taps 0-2 under this one's taps 6-8)
-              const int t2 = t + 3;
-              const int tt = t2 < TAPS ? t2 : t2 - TAPS;
-#pragma unroll
-              for (int c = 0; c < 2 * NF; ++c) a16[t2 % 4][c] = wfrag(t2 >= TAPS, c, tt);
-            }
-#endif
-#pragma unroll
-            for (int m = 0; m < MF; ++m) {
-              const int f = s * MF + m;
-              if (f + RB - 1 < NFRAG) bq[(f + RB - 1) % RB] = M::load(bptr((f + RB - 1) / MF, (f + RB - 1) % MF));
-              __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-              for (int c = 0; c < 2 * NF; ++c) {
-                const Frag& wf = a16[t % 4][c];
-                if (s & 1) { if (c & 1) M::template mma16<3>(acc[m][c >> 1], wf, bq[f % RB]); else M::template mma16<2>(acc[m][c >> 1], wf, bq[f % RB]); }
-                else { if (c & 1) M::template mma16<1>(acc[m][c >> 1], wf, bq[f % RB]); else M::template mma16<0>(acc[m][c >> 1], wf, bq[f % RB]); }
-              }
-            }
-          }
-        } else {
         Frag b16[2][MF];
 #pragma unroll
-        for (int m = 0; m < MF; ++m) {
-          if constexpr (EARLYB) b16[0][m] = b16e[m];   // read right behind the barrier
-          else b16[0][m] = M::load(bptr(0, m));
-        }
+        for (int m = 0; m < MF; ++m) b16[0][m] = M::load(bptr(0, m));
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {   // half-step s = 2*tap + pixel half
           const int t = s >> 1;
@@ -995,22 +853,10 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
               if (s & 1) { if (c & 1) M::template mma16<3>(acc[m][c >> 1], wf, b16[s & 1][m]); else M::template mma16<2>(acc[m][c >> 1], wf, b16[s & 1][m]); }
               else { if (c & 1) M::template mma16<1>(acc[m][c >> 1], wf, b16[s & 1][m]); else M::template mma16<0>(acc[m][c >> 1], wf, b16[s & 1][m]); }
             }
-          if (DEFER && s >= 1 && (s - 1) % ESTRIDE == 0 && (s - 1) / ESTRIDE < NFR) {
-            if (pend) store_frag(((s - 1) / ESTRIDE) / NF, ((s - 1) / ESTRIDE) % NF);
-          }
         }
-        if (DEFER && pend) {
-#pragma unroll
-          for (int idx = EHANDLED; idx < NFR; ++idx) store_frag(idx / NF, idx % NF);
-          pend = false;
-        }
-        }   // !WR4
       } else {
       // ring of LD+1 fragment sets: the reads of step s+LD are in flight while step s multiplies
-#ifndef IG2_LD8
-#define IG2_LD8 1
-#endif
-      constexpr int LD = (MF * NF >= 8) ? IG2_LD8 : ((MF * NF >= 4) ? 2 : 3);
+      constexpr int LD = (MF * NF >= 8) ? 1 : ((MF * NF >= 4) ? 2 : 3);
       Frag xr[LD + 1][MF];
 #pragma unroll
       for (int j = 0; j < LD; ++j)
@@ -1105,9 +951,6 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
           for (int i = 0; i < 16; ++i) { s1[q][i] = 0.f; s2[q][i] = 0.f; }
         }
       };
-#ifndef IG2_MRG
-#define IG2_MRG 1
-#endif
       // MRG (two channel fragments per wave, 16x16x32): the wave's 64 channels of a pixel are 128 contiguous bytes -- one cache
       // line -- but stored fragment by fragment every store instruction wrote sixteen HALF lines (16 pixels x 64 B).  What a
       // store costs the CU is per line touched, not per byte (a timing build without the stores ran the 3x3 launches 15 % faster,
@@ -1115,7 +958,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
       // both fragments of an output row go through one [32 px][128 B] scratch tile and leave as four instructions of eight FULL
       // lines each.  One scratch slot (LDS executes a wave's accesses in order: row m + 1 is written after row m's reads were
       // issued); the stores of row m are issued behind the packing and sums of row m + 1.
-      constexpr bool MRG = IG2_MRG && M16 && !DEFER && NF == 2 && TAPS != 1 && !PERM_EPI && !RAGGED;   // (the ragged instantiations spill 6 dwords with it)
+      constexpr bool MRG = M16 && !DEFER && NF == 2 && TAPS != 1 && !RAGGED;   // (the ragged instantiations spill 6 dwords with it)
       // (plan_v2 keeps a concat split that falls between the two fragments of a wave -- split % 64 != 0 -- off these tilings)
       constexpr bool mrg_done = MRG;
       if constexpr (MRG) {
@@ -1214,17 +1057,13 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
               packed[DEFER ? m : 0][DEFER ? q : 0][2 * g + 1] = pack_bf16x2(acc[m][q][4 * g + 2], acc[m][q][4 * g + 3]);
             }
           }
-          if (PERM_EPI) frag_store_perm(m, q, packed[0][0]);
-          else if (!DEFER) {
+          if (!DEFER) {
             frag_to_lds(packed[0][0], fidx & 1);
             if (pm_ >= 0) { frag_from_lds(tvp, (fidx - 1) & 1); frag_store(pm_, pq_, tvp); }
             pm_ = m; pq_ = q; ++fidx;
           }
           if (STATS) {
-#ifndef IG2_PKSTATS
-#define IG2_PKSTATS 1
-#endif
-            if constexpr (IG2_PKSTATS && !DEFER) {
+            if constexpr (!DEFER) {
               // un-deferred epilogue (no MFMA of this wave in flight): the 32 sum updates of a fragment as 16 packed-f32
               // instructions -- same IEEE arithmetic, half the vector issue slots on a SIMD that also hosts a producer wave
               typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -1246,7 +1085,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
           }
         }
       }
-      if (!DEFER && !PERM_EPI && !mrg_done) { frag_from_lds(tvp, (fidx - 1) & 1); frag_store(pm_, pq_, tvp); }
+      if (!DEFER && !mrg_done) { frag_from_lds(tvp, (fidx - 1) & 1); frag_store(pm_, pq_, tvp); }
       if (DEFER) { set_item(img, tyi, txi, nbi); pend = true; }
       if (STATS && !WRES) {
         if constexpr (!mrg_done) {
@@ -1265,7 +1104,6 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
     if (p.trace && blockIdx.x == 0 && wave == 0 && lane == 0 && sidx == nstage - 1) p.trace[2044] = __builtin_amdgcn_s_memrealtime();
 #endif
     cur = DMA ? (cur + 1 == NBUF ? 0 : cur + 1) : (cur ^ 1);
-    early_b(cur);
     if (++ch == p.nch) {
       ch = 0; ++item;
       if (++nbi_c == p.nblk) {

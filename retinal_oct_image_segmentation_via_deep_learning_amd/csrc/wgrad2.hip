@@ -93,31 +93,16 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
   constexpr int NPI = LH * LW, NPD = TH * TW;          // pixels of the input / dY tile
   constexpr int INB = NPI * 64, DYB = NPD * 64;        // bytes per 32-channel block
   constexpr int STAGEB = IB * INB + CB * DYB;
-#ifndef W2_DYDMA
-#define W2_DYDMA 0   /* measured (r3, same box): +3.5 % on the weight-gradient launches, see DESIGN.md */
-#endif
-  // DMA: dY needs no transform on the way in and its LDS image ([pixel][64 B], dense) is exactly the order in which the
-  // producer lanes fetch it, so it goes global -> LDS directly (global_load_lds_dwordx4, 1 KB per wave instruction): no
-  // registers, no ds_write, no commit work -- the producers' commit + issue (5.76 k cycles per stage against 5.35 k of MFMA
-  // phase, profiles/r02_wgrad2_timeline.txt) was what the stage waited for.  Ragged tiles (dY rows beyond the image must
-  // read as zero) keep the register path.
-  constexpr bool DMA = W2_DYDMA && !RAGGED;
-#ifndef W2_M16
-#define W2_M16 1
-#endif
-#ifndef W2_SWZ
-#define W2_SWZ 1
-#endif
   // W16 (3x3 kernels): v_mfma_f32_16x16x32_bf16 -- a fragment is 32 pixels (a whole tile row) x 16 channels, D = 16 co x 16 ci
   // in quarter S = 2*(co half) + (ci half) of the tap's accumulator: register 4S + e = (co 16a + 4*(lane>>4) + e, ci 16b + (lane&15)).
   // Same FLOPs, LDS reads and loop as the 32x32x16 form (pixel halves become channel halves); the chip holds a higher clock
   // on this shape (igemm2.hip, M16).
-  constexpr bool W16 = W2_M16 && TAPS == 9;
+  constexpr bool W16 = TAPS == 9;
   // SWZ: in the W16 form the two 16-lane groups that a ds_read_b64_tr_b16 services together read pixels p and p + 8 of the SAME
   // 32-byte channel half -- 512 B apart, i.e. the same banks: a 2-way conflict on every transposed read (4 LDS cycles instead
   // of 2; tools/lds_swizzle_check.py).  Pixels whose tile column has bit 3 set therefore store their two 32-B halves swapped
   // (chunk g at g ^ 2), and a reader lane takes half h ^ bit3(column).
-  constexpr bool SWZ = W2_SWZ && W16;
+  constexpr bool SWZ = W16;
   // MULTI (1 x 1 kernels only: one accumulator per pair, 16 registers): 8 or 16 pairs per workgroup, the four waves as a
   // 2 x 2 grid over (co, ci), each owning WCB x WIB pairs of the same staged tile.  A 1 x 1 weight gradient is a plain GEMM
   // over the pixels with nothing but staging between memory and the matrix pipe: with 64 x 64 blocks the deep transposed
@@ -160,16 +145,14 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
 
   if (wave >= 4) {
     // ============================== producer waves ==============================
-#ifdef W2_PROD_PRIO
-    __builtin_amdgcn_s_setprio(W2_PROD_PRIO);
-#endif
     const int ptid = tid - 256, g = ptid & 3, pb = ptid >> 2;
     constexpr int SIB = (NPI * 4 + 255) / 256;   // input slots per 32-channel block (256 producer threads)
     constexpr int SDB = (NPD * 4 + 255) / 256;   // dY slots per 32-row block
     constexpr int D = DRING;
-    struct Stage { u32x4 ri[IB][SIB]; u32x4 rd[DMA ? 1 : CB][DMA ? 1 : SDB]; unsigned vm[IB]; unsigned vd; int img, tyi, txi; };
+    // (img, tyi, txi: written by issue(), read by nothing since the LDS-DMA staging of dY was removed; without them hipcc
+    //  numbers the registers of the depth-tap instantiation differently, so they stay until the loop is next touched)
+    struct Stage { u32x4 ri[IB][SIB]; u32x4 rd[CB][SDB]; unsigned vm[IB]; unsigned vd; int img, tyi, txi; };
     Stage R[D];
-    const int pw = __builtin_amdgcn_readfirstlane(wave) - 4;   // producer wave 0..3, scalar: the LDS-DMA destination is wave-uniform
     // per-slot constants (shared by all blocks): pixel offset from the tile origin + border code
     int reli[SIB], reld[SDB];
     int lyv[RSH ? SIB : 1];   // RSH: local row of the slot
@@ -245,7 +228,6 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
         }
         S.vm[blk] = vm;
       }
-      if constexpr (!DMA) {
 #pragma unroll
       for (int blk = 0; blk < CB; ++blk) {
         const int row = co_sb + blk * 32;  // GEMM row = output channel (or (dydx, co) for the deconv)
@@ -272,43 +254,6 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
         }
         if (RAGGED) S.vd = vd;
       }
-      }
-    };
-    // dY tile of the stage whose coordinates `S` holds -> LDS, no registers in between.  Lane i of producer wave pw fetches
-    // the 16 B that belong at byte (256 j + 64 pw + i) * 16 of the block: one contiguous KB per instruction.
-    typedef __attribute__((address_space(3))) void lds_void;
-    typedef const __attribute__((address_space(1))) void gl_void;
-    auto dma_dy = [&](unsigned char* buf, const Stage& S) {
-      const int img = S.img, tyi = S.tyi, txi = S.txi;
-#pragma unroll
-      for (int blk = 0; blk < CB; ++blk) {
-        const int row = co_sb + blk * 32;
-        const bf16_t* base;
-        int cs;
-        if (p.dy_mode == OCT_IN_S2D) {
-          cs = p.cout >> 2;
-          const int dydx = row / cs, co = row - dydx * cs;
-          const int img2 = (D3 && p.dy_mul) ? img * p.dy_mul + p.dy_add : img;
-          const size_t o2 = ((size_t)img2 * (2 * p.h) + 2 * tyi * TH + (dydx >> 1)) * (size_t)(2 * p.w) + 2 * txi * TW + (dydx & 1);
-          base = p.dy + o2 * cs + co;
-        } else {
-          cs = p.cout;
-          base = p.dy + (((size_t)img * p.h + tyi * TH) * p.w + txi * TW) * cs + row;
-        }
-        unsigned char* const dst = buf + IB * INB + blk * DYB + pw * 1024;
-#pragma unroll
-        for (int j = 0; j < SDB; ++j)   // a DMA writes LDS in lane order: the swizzle goes on the source chunk
-          __builtin_amdgcn_global_load_lds((gl_void*)(base + __mul24(reld[j], cs) + (int)(((unsigned)g ^ dswz[j]) * 8u)), (lds_void*)(dst + j * 4096), 16, 0, 0);
-      }
-    };
-    // s_waitcnt vmcnt(N), everything else at its maximum (gfx9 encoding: vmcnt = simm16[15:14 | 3:0])
-    constexpr int NXL = IB * SIB;   // input loads of one stage: issued AFTER the stage's DMA, they stay in flight across the wait
-    constexpr int WAIT_DMA = (NXL & 15) | ((NXL >> 4) << 14) | (7 << 4) | (0 << 8);   // ... and lgkmcnt(0): the commit's ds_writes
-    // Stage barrier of the producers.  With a DMA in the stage it is the counted wait + a raw s_barrier: __syncthreads()
-    // would add vmcnt(0) (the pending LDS write of a DMA sits on the VM counter) and drain the prefetched stages too.
-    auto stage_barrier = [&]() {
-      if constexpr (DMA) { __builtin_amdgcn_s_waitcnt(WAIT_DMA); asm volatile("s_barrier" ::: "memory"); }
-      else __syncthreads();
     };
     auto commit = [&](unsigned char* buf, const Stage& S) {
 #pragma unroll
@@ -317,7 +262,6 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
         const bool second = cg >= p.c0;
         const bool xf = second ? (p.xf1 != 0) : (p.xf0 != 0);
         const float flo = xf_floor(second ? p.xf1 : p.xf0);   // wave-uniform: 0 (BN + ReLU) or -inf (plain affine)
-        const unsigned flo_pk = xf_floor_pk(second ? p.xf1 : p.xf0);
         float s[8], b[8];
         if (xf) {
           const float* sc = sxf + blk * 32 + g * 8;
@@ -334,14 +278,9 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
             if (xf) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                if (OCT_PK_RELU) {
-                  v[e] = pk_clamp_bf16(w2_pack(fmaf(__uint_as_float(v[e] << 16), s[2 * e], b[2 * e]),
-                                               fmaf(__uint_as_float(v[e] & 0xffff0000u), s[2 * e + 1], b[2 * e + 1])), flo_pk);
-                } else {
                 const float lo = fmaxf(fmaf(__uint_as_float(v[e] << 16), s[2 * e], b[2 * e]), flo);
                 const float hi = fmaxf(fmaf(__uint_as_float(v[e] & 0xffff0000u), s[2 * e + 1], b[2 * e + 1]), flo);
                 v[e] = w2_pack(lo, hi);
-                }
               }
             }
             const bool live = ((S.vm[blk] >> j) & 1u) != 0;
@@ -351,7 +290,6 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
           }
         }
       }
-      if constexpr (!DMA)
 #pragma unroll
       for (int blk = 0; blk < CB; ++blk)
 #pragma unroll
@@ -369,12 +307,8 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
 #pragma unroll
     for (int j = 0; j < D; ++j) issue(min(j, last), R[j]);
     commit(smem, R[0]);
-    if constexpr (DMA) dma_dy(smem, R[0]);
     issue(min(D, last), R[0]);
-    // The DMA sits between this stage's commit (whose registers were waited for with a COUNTED vmcnt: no DMA was pending
-    // then) and the next loads; the explicit wait retires it and leaves those loads in flight.  It must be the builtin:
-    // hipcc has to see the DMA retired, or every later wait of the ring becomes vmcnt(0).
-    stage_barrier();
+    __syncthreads();
     // branch-free steady state over the padded stage count (see igemm2.hip)
     for (int s0 = 0; s0 < nstage_pad; s0 += D) {
 #pragma unroll
@@ -382,11 +316,10 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
         const int nx = s0 + j + 1;
         if (wave == 4) W2TRACE(4, nx - 1);
         commit(smem + (nx & 1) * STAGEB, R[(j + 1) % D]);
-        if constexpr (DMA) dma_dy(smem + (nx & 1) * STAGEB, R[(j + 1) % D]);   // stage nx's tile: buffer nx & 1 was last read in stage nx - 2
         if (wave == 4) W2TRACE(5, nx - 1);
         issue(min(nx + D, last), R[(j + 1) % D]);
         if (wave == 4) W2TRACE(6, nx - 1);
-        stage_barrier();
+        __syncthreads();
         if (wave == 4) W2TRACE(7, nx - 1);
       }
     }
@@ -394,10 +327,7 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
   }
 
   // ================================ MFMA waves ================================
-#ifndef W2_MFMA_PRIO
-#define W2_MFMA_PRIO 3
-#endif
-  __builtin_amdgcn_s_setprio(W2_MFMA_PRIO);  // win issue arbitration against the co-resident producer wave
+  __builtin_amdgcn_s_setprio(3);  // win issue arbitration against the co-resident producer wave
   const int pair = MULTI ? 0 : wave % PAIRS, psx = MULTI ? 0 : wave / PAIRS;
   const int cb = MULTI ? (wave >> 1) * WCB : pair / IB, ib = MULTI ? (wave & 1) * WIB : pair % IB;   // MULTI: first pair of the wave's sub-block
   const int g4 = lane >> 4, li = lane & 15;
@@ -480,12 +410,9 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
         if constexpr (SWZ) { const int rc = ((k >> 1) * TW) * 64; return tr_frag2(dy1[k & 1] + rc, dy1[k & 1] + rc + 4 * 64); }
         else return tr_frag(dy_t + ao(k));
       };
-      // input fragments run LA iterations (up to 3 MFMAs = 96 matrix cycles each) ahead of their use.  LA = 2 left the
-      // reads ~190 cycles of lead, about one loaded-LDS round trip; W2_LA (default 4) doubles it for 8 VGPRs.
-#ifndef W2_LA
-#define W2_LA 2   /* A/B on the box (LA = 2, 4, 6): no difference on any launch -- the kernel is not LDS-latency bound */
-#endif
-      constexpr int LA = W2_LA;
+      // input fragments run LA iterations (up to 3 MFMAs = 96 matrix cycles each) ahead of their use.  LA = 2 leaves the
+      // reads ~190 cycles of lead, about one loaded-LDS round trip; LA = 4 would double it for 8 VGPRs.
+      constexpr int LA = 2;   // A/B on the box (LA = 2, 4, 6): no difference on any launch -- the kernel is not LDS-latency bound
       bf16x8 aw[4][2];
       bf16x8 bq[LA + 1];
       aw[0][0] = dy_frag(0);

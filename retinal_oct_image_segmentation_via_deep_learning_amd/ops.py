@@ -100,9 +100,8 @@ NBT_PENDING = []   # BatchNorm step counters of the ops run since the last flush
 # 2x' + q + tx - 1 = 2(x' + d) + p.  Half of W' is zero -- twice the FLOPs, on layers that are HBM-bound: the generic kernels ran the
 # eight 16-channel convolutions and four weight gradients of MGU-Net's first level in 7.6 of its 18.8 ms per step.  Only host code:
 # views of the activations, the folded filter (a gather), the two parities of the BatchNorm partial sums added, the filter gradient
-# un-folded (an index_add).  OCT_FOLD16=0 switches it off.
+# un-folded (an index_add).
 # --------------------------------------------------------------------------------------------------------------------
-FOLD16 = [os.environ.get("OCT_FOLD16", "1") != "0"]
 _FOLD_TX = {}
 
 
@@ -115,7 +114,7 @@ def _fold_tx(dev):
 
 
 def fold16_ok(e, taps, kk, wd, c0, c1, cout) -> bool:
-    return (FOLD16[0] and e.dt == L.DT_BF16 and taps in (1, 9) and kk is None and wd % 2 == 0 and wd >= 4 and c0 % 16 == 0 and c1 % 16 == 0
+    return (e.dt == L.DT_BF16 and taps in (1, 9) and kk is None and wd % 2 == 0 and wd >= 4 and c0 % 16 == 0 and c1 % 16 == 0
             and cout % 16 == 0 and bool(c0 % 32 or c1 % 32 or cout % 32))
 
 
@@ -176,7 +175,7 @@ def unfold16_deconv_wgrad(dwf, cin, cout):
 
 
 def fold16_deconv_ok(e, k, wd, cin, cout) -> bool:
-    return (FOLD16[0] and e.dt == L.DT_BF16 and k == 2 and wd % 2 == 0 and cin % 16 == 0 and cout % 16 == 0 and bool(cin % 32 or cout % 32))
+    return (e.dt == L.DT_BF16 and k == 2 and wd % 2 == 0 and cin % 16 == 0 and cout % 16 == 0 and bool(cin % 32 or cout % 32))
 
 
 def _fold_src(x0, c0, xf0, x1, c1, xf1):

@@ -51,11 +51,6 @@ class BasicBlock(HipModule):
         return self._out(self.nhwc(self._in(input)))
 
 
-# OCT_POOL_CODES=0: the network's internal pool -> un-pool path on torch's int64 indices (the public block API always uses them)
-import os as _os
-_WINDOW_CODES = [_os.environ.get("OCT_POOL_CODES", "1") != "0"]
-
-
 class EncoderBlock(BasicBlock):
     def __init__(self, params, compute_dtype="bf16"):
         super().__init__(params, compute_dtype)
@@ -149,7 +144,7 @@ class ReLayNet(SegLossMixin, HipModule):
                                f"{input.shape[3]} is not divisible by {self._div} (three {self._div ** (1 / 3):.0f}x poolings "
                                f"followed by as many unpoolings)")
         a = self._in(input)
-        codes = _WINDOW_CODES[0]
+        codes = True   # one-byte window codes inside the network; the public block API keeps int64 indices
         e1, out1, ind1 = self.encode1.nhwc(a, codes)
         e2, out2, ind2 = self.encode2.nhwc(e1, codes)
         e3, out3, ind3 = self.encode3.nhwc(e2, codes)
