@@ -188,6 +188,34 @@ int oct_conv_wgrad_fused_apply_ok(const OctWgradDesc* d);
 /* 1 when oct_conv_wgrad accepts in_img_shift = OCT_IMG_SHIFT_ALL for this descriptor (nn.Conv3d(1, F, 3) weight gradient,
  * engine3d: all 27 taps in one pass over dY instead of three), else 0.  Host-only query, never fails.    */
 int oct_conv_wgrad_all_depth_taps_ok(const OctWgradDesc* d);
+/* Fused backward of a 3x3 convolution with 32 input and 32 output channels whose input is x = relu(bn(y1)) of the
+ * convolution below (the second convolution of a U-Net block at full resolution, YNet_2022.py:578-600).  ONE launch reads
+ * dY once and produces
+ *   dx       = the data gradient dA1, bit-identical to oct_conv_forward with OCT_PACK_CONV_DGRAD weights on dY;
+ *   dwp      = the weight gradient [9][cout][cin] as oct_conv_wgrad writes it (fp32 atomics, caller zeroes), for
+ *              oct_unpack_wgrad_batch;
+ *   partials = the BatchNorm-backward sums of the layer below, [oct_conv_backward_fused_blocks][2][cin]: sum of g and of
+ *              g * (y1 - mean) * invstd with g = [y1*scale + shift > 0] ? dA1 (as stored) : 0 -- the rows oct_dact_bn_reduce
+ *              would write from dx and y1, for oct_bn_bwd_finalize.  One row per workgroup, summed in a fixed order: the
+ *              same bits on every run.
+ * in place of oct_conv_wgrad + oct_conv_forward + oct_dact_bn_reduce (three of their passes over a tensor fall away).
+ * The descriptor is the layer's OctWgradDesc.  oct_conv_backward_fused_ok is 1 only for bf16, 2-D, taps 9, c0 = cout = 32,
+ * c1 = 0, xform0 = OCT_XF_AFFINE_RELU, plain dY, w % 32 == 0, h % 8 == 0, partials = 0 and OCT_DISABLE_V2 unset; for every
+ * other descriptor it is 0, _blocks is 0, the launch returns OCT_E_INVALID without touching its outputs, and the caller
+ * keeps the three separate launches.  Host-only queries, never fail.                                              */
+typedef struct OctConvBwdFusedArgs {
+  const void* x;                            /* raw input y1 of the layer, NHWC [n,h,w,32] */
+  const float* scale; const float* shift;   /* its BN + ReLU transform (xform0) */
+  const float* mean; const float* invstd;   /* BatchNorm statistics of the layer below */
+  const void* dy;                           /* gradient wrt the layer's output, NHWC [n,h,w,32] */
+  const void* wpacked;                      /* the layer's weight, OCT_PACK_CONV_DGRAD */
+  void* dx;                                 /* NHWC [n,h,w,32] */
+  float* dwp;                               /* [9][32][32] fp32, zeroed by the caller */
+  float* partials;                          /* [oct_conv_backward_fused_blocks][2][32] fp32 */
+} OctConvBwdFusedArgs;
+int oct_conv_backward_fused_ok(const OctWgradDesc* d);
+int oct_conv_backward_fused_blocks(const OctWgradDesc* d);
+int oct_conv_backward_fused(const OctWgradDesc* d, const OctConvBwdFusedArgs* a, void* stream);
 /* dwp -> torch-layout gradient.  mode: OCT_PACK_CONV_FPROP (grad[co][ci][tap]),
  * OCT_PACK_DECONV_FPROP (grad[ci][co][dydx]) or OCT_PACK_1X1_FPROP (grad[co][ci]).
  * accumulate != 0: grad += */

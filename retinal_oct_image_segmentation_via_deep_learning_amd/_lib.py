@@ -65,6 +65,10 @@ class WgradArgs(C.Structure):
                                                 "dy_y", "dy_coef", "dy_scale", "dy_shift", "dbias_partials")]
 
 
+class ConvBwdFusedArgs(C.Structure):   # struct OctConvBwdFusedArgs
+    _fields_ = [(k, c_void_p) for k in ("x", "scale", "shift", "mean", "invstd", "dy", "wpacked", "dx", "dwp", "partials")]
+
+
 class HeadDesc(C.Structure):
     _fields_ = [(k, c_int) for k in ("dtype", "n", "h", "w", "feat", "classes")]
 
@@ -104,6 +108,9 @@ SIGNATURES = {
     "oct_conv_wgrad": (c_int, [C.POINTER(WgradDesc), C.POINTER(WgradArgs), c_void_p]),
     "oct_conv_wgrad_fused_apply_ok": (c_int, [C.POINTER(WgradDesc)]),
     "oct_conv_wgrad_all_depth_taps_ok": (c_int, [C.POINTER(WgradDesc)]),
+    "oct_conv_backward_fused_ok": (c_int, [C.POINTER(WgradDesc)]),
+    "oct_conv_backward_fused_blocks": (c_int, [C.POINTER(WgradDesc)]),
+    "oct_conv_backward_fused": (c_int, [C.POINTER(WgradDesc), C.POINTER(ConvBwdFusedArgs), c_void_p]),
     "oct_conv_wgrad_partials": (c_int, [C.POINTER(WgradDesc)]),
     "oct_reduce_bias_partials": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "oct_unpack_wgrad": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

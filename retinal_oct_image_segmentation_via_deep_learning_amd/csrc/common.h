@@ -47,6 +47,9 @@ int launch_roll3d(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a
 int launch_igemm2(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s);
 int launch_gemm1(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s);
 int launch_igemm(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s);
+// igemm2.hip, fused backward of a 32 -> 32 layer (oct_conv_backward_fused): false = not eligible; stat_rows = rows of partials
+bool igemm2_fused_plan(const OctWgradDesc* d, ConvPlan* pl);
+int launch_igemm2_fused(const ConvPlan& pl, const OctWgradDesc* d, const OctConvBwdFusedArgs* a, hipStream_t s);
 
 enum WgradPath { WGRAD_FIRST, WGRAD_W2, WGRAD_GENERIC };
 struct WgradPlan {
@@ -177,6 +180,28 @@ template <> struct Mma<float> {
     if (j < 4) f.lo[j] = v; else f.hi[j - 4] = v;
   }
 };
+
+// ---- transposed LDS reads (ds_read_b64_tr_b16): the contraction index of a [pixel][channel] tile onto the MFMA k axis ----
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+// one MFMA operand fragment (8 contraction pixels per lane) through two transposed LDS reads
+__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base_lo) {
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo));
+  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo + 4 * 64));  // pixels +4
+  typedef short s16x8 __attribute__((ext_vector_type(8)));
+  const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// the same with the two reads addressed separately (swizzled tiles: the second read's half can differ per lane)
+__device__ __forceinline__ bf16x8 tr_frag2(const unsigned char* first, const unsigned char* second) {
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(first));
+  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(second));
+  typedef short s16x8 __attribute__((ext_vector_type(8)));
+  const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  return __builtin_bit_cast(bf16x8, v);
+}
 
 // sum over the 64 lanes of a wave
 __device__ __forceinline__ float wave_sum(float v) {

@@ -141,3 +141,30 @@ extern "C" int oct_conv_wgrad(const OctWgradDesc* d, const OctWgradArgs* a, void
     default: return launch_wgrad(pl, d, a, s);
   }
 }
+
+// Fused backward of a 32 -> 32 layer (igemm2.hip, FUSE): the library decides, the caller asks.  OCT_DISABLE_V2=1 switches it
+// off with the other pipelined kernels.
+static bool plan_conv_backward_fused(const OctWgradDesc* d, ConvPlan* pl) {
+  return d && v2_enabled() && igemm2_fused_plan(d, pl);
+}
+
+extern "C" int oct_conv_backward_fused_ok(const OctWgradDesc* d) {
+  ConvPlan pl;
+  return plan_conv_backward_fused(d, &pl) ? 1 : 0;
+}
+
+extern "C" int oct_conv_backward_fused_blocks(const OctWgradDesc* d) {
+  ConvPlan pl;
+  return plan_conv_backward_fused(d, &pl) ? pl.stat_rows : 0;
+}
+
+extern "C" int oct_conv_backward_fused(const OctWgradDesc* d, const OctConvBwdFusedArgs* a, void* stream) {
+  OCT_CHECK(d && a, "oct_conv_backward_fused: null descriptor");
+  ConvPlan pl;
+  OCT_CHECK(plan_conv_backward_fused(d, &pl),
+            "oct_conv_backward_fused: not available for this descriptor (oct_conv_backward_fused_ok): bf16, 2-D, 3x3, c0 = cout = 32, "
+            "c1 = 0, BN + ReLU on load, w %% 32 == 0, h %% 8 == 0, atomics mode");
+  OCT_CHECK(a->x && a->scale && a->shift && a->mean && a->invstd && a->dy && a->wpacked && a->dx && a->dwp && a->partials,
+            "oct_conv_backward_fused: null tensor");
+  return launch_igemm2_fused(pl, d, a, as_stream(stream));
+}

@@ -29,6 +29,10 @@ struct Igemm2Params {
   // 3-D (see OctConvDesc.depth): nchc = 32-channel chunks per depth tap; chunk ch = kd*nchc + c reads slice d + kd - 1.
   // S2D with depth: k = (kd, dy, dx, c) gathers from slice 2d + kd.  D2S: output image = img*oimg_mul + oimg_add.
   int depth, nchc, oimg_mul, oimg_add;
+  // FUSE (oct_conv_backward_fused): the layer's raw input with its BN + ReLU transform, the BatchNorm statistics of the layer
+  // below, and the two extra outputs dwp[tap][cout][cin] (atomics) and bnpart[workgroup][2][cin]
+  const bf16_t* fx; const float* fsc; const float* fsh; const float* fmean; const float* finvstd;
+  float* dwp; float* bnpart;
   unsigned long long* trace;  // diagnostic builds only (-DOCT_TRACE): s_memtime stamps of workgroup 0
 };
 
@@ -87,10 +91,25 @@ __device__ __attribute__((aligned(16))) unsigned int g_zero16[4];
 // waves fetched all 36 fragments per 16 x 32 tile -- 144 KB of weight requests next to 78 KB of activations on the
 // full-resolution layer, through the same per-CU load path: it ran at 3.9 TB/s where its 32 -> 32 siblings (resident
 // weights in registers) reach 5.4.  Registers cannot hold 36 fragments (144 VGPRs) beside the accumulators.
+// FUSE (the 32 -> 32 resident-weight data gradient on whole 8-row tiles): the same launch also produces the layer's weight
+// gradient and the BatchNorm-backward sums of the layer below, from what is on chip anyway.
+//  * dW[t][co][ci] = sum over the tile's OWN pixels q of dY[q - (t - 1)][co] * x[q][ci]: dY on the tile plus a one-pixel halo
+//    (zero outside the image) is the staged LDS tile; the only new operand is the interior tile of x = relu(bn(y1)), which
+//    the producers stage next to it (same transform and rounding as wgrad2's).  Three of the four PRODUCER waves take one tap
+//    row each (48 accumulator registers), contract over the pixels with transposed LDS reads while the MFMA waves work on
+//    dX of the same stage, and add their accumulators to dwp with fp32 atomics once, after the persistent tile loop.
+//  * g = [y1*scale + shift > 0] ? dA1 : 0 with dA1 as stored (after the bf16 pack): the epilogue lane that stores 16 B of dA1
+//    reads the same 16 B of raw y1 from a second (untransformed) interior tile in LDS -- the lane -> (pixel, 8 channels) map of
+//    the store is fixed, so every lane keeps 2 x 8 running sums; one row [2][cin] per workgroup, summed in a fixed order.
+//    (The raw tile and not a re-read through L2: a global load in the MFMA waves would sit in the in-order vmcnt queue behind
+//    the previous row's output stores; not the transform on the transposed fragments either: all four waves read every x
+//    fragment, so each would redo the producers' work.)
 template <int TAPS, int WM, int WN, int MF, int NF, bool WRES, bool STATS, bool RAGGED = false, bool D3 = false, bool DMA = false,
-          bool WLDS = false>
+          bool WLDS = false, bool FUSE = false>
 __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
   static_assert(WM * WN == 4, "four MFMA waves");
+  static_assert(!FUSE || (TAPS == 9 && WM == 4 && NF == 1 && WRES && !STATS && !RAGGED && !D3 && !DMA && !WLDS),
+                "fused backward: resident weights, 32 -> 32 channels, whole tiles, 2-D");
   static_assert(!DMA || (!WRES && !STATS && !RAGGED && !D3), "DMA staging: streamed weights, whole tiles, 2-D, no BatchNorm sums");
   static_assert(!WLDS || (TAPS == 9 && !WRES && !D3 && !DMA && WN * NF == 1), "LDS-resident weights: 3x3, one 32-channel block");
   constexpr int TH = WM * MF, TW = 32;
@@ -158,6 +177,10 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
   // streamed-weight kernels: BatchNorm partial sums of ALL items of this workgroup, [2][cout]; one row
   // per workgroup reaches memory instead of one per tile (bn_finalize then reads <= 512 rows, not 16 k)
   float* const wgacc = sbias + SBIAS_N;
+  // FUSE: interior tiles of x, [2 buffers][TH * 32 pixels][64 B] each: transformed (dW operand), then raw (BatchNorm sums)
+  constexpr int XTB = TH * TW * 64;
+  unsigned char* const fxt = reinterpret_cast<unsigned char*>(sbias + SBIAS_N);
+  unsigned char* const fxr = fxt + 2 * XTB;
   if (STATS && !WRES) {
     for (int i = tid; i < 2 * p.cout; i += 512) wgacc[i] = 0.f;
   }
@@ -171,6 +194,9 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
     }
     if (d2s && p.bias)
       for (int i = tid; i < (p.cout >> 2); i += 512) sbias[i] = p.bias[i];
+    if constexpr (FUSE) {   // per channel {scale, shift, mean, invstd} of the layer below: one ds_read_b128 in the epilogue
+      if (tid < 32) *reinterpret_cast<f32x4*>(sxf + SXF_N + 4 * tid) = f32x4{p.fsc[tid], p.fsh[tid], p.fmean[tid], p.finvstd[tid]};
+    }
     if constexpr (WLDS) {   // the filter of this 32-channel block, packed fragment order as it lies in memory
       const u32x4* src = reinterpret_cast<const u32x4*>(p.wp);
       u32x4* dst = reinterpret_cast<u32x4*>(wlds);
@@ -293,6 +319,24 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
       c |= (ly >= ylast ? 2u : 0u) | (lx >= xlast ? 8u : 0u);
       code[i] = c;
     }
+    // FUSE: the interior tile of x rides the same ring, XS slots of 16 B per thread and stage (never out of the image)
+    constexpr int XS = FUSE ? TH * TW * 4 / 256 : 1;
+    u32x4 XR[D][XS];
+    unsigned xrel[XS];
+    float fs[8], fb[8];
+    const unsigned char* x_next = nullptr;   // x at the origin of the tile issue_begin() last returned (+ this lane's 16 B)
+    if constexpr (FUSE) {
+#pragma unroll
+      for (int i = 0; i < XS; ++i) {
+        const int pix = pbase + 64 * i;
+        xrel[i] = (unsigned)((pix >> 5) * p.w + (pix & 31)) * 64u;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { fs[j] = p.fsc[grp * 8 + j]; fb[j] = p.fsh[grp * 8 + j]; }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // once, before the ring starts (see the resident filter below)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(fs[j]), "+v"(fb[j]));
+    }
     // Stages are issued and committed strictly in order (0, 1, 2, ... clamped at the last one), so the
     // (chunk, tile x, tile y, image) of the next stage are counters: the five integer divisions they replace
     // were ~150 scalar instructions per stage on the producer's critical path.
@@ -333,6 +377,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
         srcimg = zok ? img + kdi - 1 : img;
       }
       const size_t origin = ((size_t)srcimg * p.h + tyi * TH) * p.w + txi * TW;
+      if constexpr (FUSE) x_next = reinterpret_cast<const unsigned char*>(p.fx + origin * 32 + grp * 8);
       const bool second = !s2d && chc * 32 >= p.c0;  // uniform: a 32-channel chunk lies in one source
       const int cs = second ? p.c1 : p.c0;
       const bf16_t* base;
@@ -418,10 +463,80 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
 #pragma unroll
       for (int i = 0; i < NSLOT; ++i) commit_slot(st, buf, i, Rr[i], vm, false);
     };
+    auto issue_x = [&](u32x4 (&Xr)[XS]) {   // right behind issue(): the same tile
 #pragma unroll
-    for (int j = 0; j < D; ++j) issue(R[j], vmask[j]);   // stages past the end re-read the last one
+      for (int i = 0; i < XS; ++i) Xr[i] = *reinterpret_cast<const u32x4*>(x_next + xrel[i]);
+    };
+    auto commit_x = [&](int bi, const u32x4 (&Xr)[XS]) {
+#pragma unroll
+      for (int i = 0; i < XS; ++i) {
+        const int off = bi * XTB + (pbase + 64 * i) * 64 + grp * 16;
+        u32x4 v = Xr[i];
+        *reinterpret_cast<u32x4*>(fxr + off) = v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float lo = fmaxf(fmaf(bf16lo(v[j]), fs[2 * j], fb[2 * j]), 0.f);
+          const float hi = fmaxf(fmaf(bf16hi(v[j]), fs[2 * j + 1], fb[2 * j + 1]), 0.f);
+          v[j] = pack_bf16x2(lo, hi);
+        }
+        *reinterpret_cast<u32x4*>(fxt + off) = v;
+      }
+    };
+    // FUSE, dW: while the MFMA waves multiply stage s (dX), three of the producer waves contract the same stage's dY halo
+    // tile with its x tile over the pixels -- producer wave pw owns tap row pw (taps 3 pw .. 3 pw + 2: 48 accumulator
+    // registers, which the MFMA waves do not have beside their 72 resident weight registers; with the taps there the
+    // compiler spilled 42 registers).  A k-step is 16 pixels of a tile row: x pixel (y, x) meets dY at halo-tile pixel
+    // (y + 2 - ty, x + 2 - tx).  Transposed read, lane 16 g4 + li: pixel 8 (g4 >> 1) + (li >> 2) of the k-step, channels
+    // 16 (g4 & 1) + 4 (li & 3) .. + 3; the lane receives channel 16 (g4 & 1) + li at pixels 8 (g4 >> 1) .. + 3 (second read:
+    // + 4) -- the 32x32x16 operand.  The x tile's 64-B pixels are conflict-free; the dY tile's 80-B pitch puts the fourth
+    // pixel of a read on 12 of the first pixel's banks (a partial 2-way conflict, tools/lds_swizzle_check.py).
+    f32x16 dwa[FUSE ? 3 : 1];
+    const int pw = wave - 4;
+    int f_trx = 0, f_trd = 0;
+    if constexpr (FUSE) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) dwa[j][i] = 0.f;
+      const int g4 = lane >> 4, li = lane & 15;
+      f_trx = (8 * (g4 >> 1) + (li >> 2)) * 64 + (16 * (g4 & 1) + 4 * (li & 3)) * 2;
+      f_trd = (8 * (g4 >> 1) + (li >> 2)) * PIXB + (16 * (g4 & 1) + 4 * (li & 3)) * 2 + (pw < 3 ? (2 - pw) * LW * PIXB : 0);
+    }
+    auto dw_stage = [&](int bi) __attribute__((always_inline)) {
+      const unsigned char* const xt = fxt + bi * XTB + f_trx;
+      const unsigned char* const dt = buf0 + bi * BUFB + f_trd;
+      constexpr int NKW = TH * 2;
+      auto xfrag = [&](int k) { return tr_frag(xt + ((k >> 1) * TW + (k & 1) * 16) * 64); };
+      auto dfrag = [&](int k, int j) {
+        const unsigned char* const a = dt + ((k >> 1) * LW + (k & 1) * 16 + (2 - j)) * PIXB;
+        return tr_frag2(a, a + 4 * PIXB);
+      };
+      Frag xq[2], dq[2][3];
+      xq[0] = xfrag(0);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dq[0][j] = dfrag(0, j);
+#pragma unroll
+      for (int k = 0; k < NKW; ++k) {
+        if (k + 1 < NKW) {
+          xq[(k + 1) & 1] = xfrag(k + 1);
+#pragma unroll
+          for (int j = 0; j < 3; ++j) dq[(k + 1) & 1][j] = dfrag(k + 1, j);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) M::mma(dwa[j], dq[k & 1][j], xq[k & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+#pragma unroll
+    for (int j = 0; j < D; ++j) {   // stages past the end re-read the last one
+      issue(R[j], vmask[j]);
+      if constexpr (FUSE) issue_x(XR[j]);
+    }
     commit(buf0, R[0], vmask[0]);
+    if constexpr (FUSE) commit_x(0, XR[0]);
     issue(R[0], vmask[0]);
+    if constexpr (FUSE) issue_x(XR[0]);
     __syncthreads();
     // Stage k lives in ring slot k % D; while the MFMA waves work on stage cs, stage cs+1 is written to
     // the other LDS buffer and its slot is refilled with the loads of stage cs+1+D.  The body is
@@ -434,7 +549,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
     // load path, and while a burst of HBM-missing tile loads sat in it the weight loads' latency exceeded the ring's lead
     // (profiles/r03_ig2_traces.txt: stages that coincide with a new tile's loads ran 30-60 % longer).
     // (not the resident-weight kernels: their MFMA waves load nothing, and an HBM-bound kernel wants its requests out early)
-    const bool spread = TAPS != 1 && !D3 && !WRES && p.xf0 != 0 && (p.c1 == 0 || p.xf1 != 0);
+    const bool spread = TAPS != 1 && !D3 && !WRES && p.xf0 != 0 && (p.c1 == 0 || p.xf1 != 0);   // (never with FUSE: WRES)
     if (spread) {
       for (int s0 = 0; s0 < nstage_pad; s0 += D) {
 #pragma unroll
@@ -466,14 +581,31 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
         const int nx = s0 + j + 1;
         if (wave == 4) TRACE(4, nx - 1);
         commit(buf0 + (nx & 1) * BUFB, R[(j + 1) % D], vmask[(j + 1) % D]);
+        if constexpr (FUSE) commit_x(nx & 1, XR[(j + 1) % D]);
         if (wave == 4) TRACE(5, nx - 1);
         issue(R[(j + 1) % D], vmask[(j + 1) % D]);
+        if constexpr (FUSE) {
+          issue_x(XR[(j + 1) % D]);
+          if (pw < 3 && nx - 1 < nstage) dw_stage((nx - 1) & 1);   // wave-uniform; the padded stages repeat the last one
+        }
         if (wave == 4) TRACE(6, nx - 1);
         __syncthreads();
         if (wave == 4) TRACE(7, nx - 1);
       }
     }
-    if (STATS) __syncthreads();  // matches the barrier of the final statistics reduction
+    if constexpr (FUSE) {   // dW: D[row = co][col = ci] of the wave's three taps, once per workgroup
+      if (pw < 3) {
+        const int r = lane & 31, hh = lane >> 5;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int co = (i & 3) + 8 * (i >> 2) + 4 * hh;
+            atomicAdd(&p.dwp[((3 * pw + j) * 32 + co) * 32 + r], dwa[j][i]);
+          }
+      }
+    }
+    if (STATS || FUSE) __syncthreads();  // matches the barrier of the final statistics reduction
     return;
   }
 
@@ -484,6 +616,13 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
   const int r = lane & 31, hh = lane >> 5;
   const int wm = wave / WN, wn = wave % WN;
 
+  // FUSE: this lane's epilogue chunks are always channels 8 * (lane & 3) .. + 7 (frag_from_lds): their running BatchNorm
+  // sums (the coefficients come from LDS)
+  float bs1[FUSE ? 8 : 1], bs2[FUSE ? 8 : 1];
+  if constexpr (FUSE) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { bs1[j] = 0.f; bs2[j] = 0.f; }
+  }
   Frag wres[WRES ? KSTEPS : 1][NF];
   if (WRES) {
 #pragma unroll
@@ -669,6 +808,8 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
       };
       unsigned pk[8];
       u32x4 tv[2];
+      u32x4 rv[FUSE ? 2 : 1];   // FUSE: raw y1 at the pixels / channels of tv
+      f32x4 co[FUSE ? 4 : 1];   //       {scale, shift, mean, invstd} of four of the lane's eight channels
       auto epi = [&](int mp, int s) __attribute__((always_inline)) {   // piece s (1..10) of the epilogue of output row mp
         if (s == 1) {
           if (RAGGED && STATS) {   // ragged last tile: pixels outside the image must not reach the BatchNorm sums
@@ -692,6 +833,35 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
           }                                                        // all of them behind the stage's barrier
         }
         if (s == 6) frag_from_lds(tv);
+        if constexpr (FUSE) {
+          if (s == 6) {
+            const unsigned char* const rt = fxr + cur * XTB + (wm * MF + mp) * (TW * 64) + lane * 16;
+            rv[0] = *reinterpret_cast<const u32x4*>(rt);
+            rv[1] = *reinterpret_cast<const u32x4*>(rt + 64 * 16);
+          }
+          // the sums of oct_dact_bn_reduce on dA1 as stored, four channels (two dwords of both chunks) at a time
+          if (s == 7 || s == 9) {
+            const float* const ct = sxf + SXF_N + 4 * (8 * (lane & 3) + (s == 7 ? 0 : 4));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) co[j] = *reinterpret_cast<const f32x4*>(ct + 4 * j);
+          }
+          if (s == 8 || s == 11) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+#pragma unroll
+              for (int e2 = 0; e2 < 2; ++e2) {
+                const int e = (s == 8 ? 0 : 2) + e2;
+                const f32x4 c0 = co[2 * e2], c1 = co[2 * e2 + 1];
+                const float y0 = bf16lo(rv[k][e]), y1 = bf16hi(rv[k][e]);
+                const float g0 = fmaf(y0, c0[0], c0[1]) > 0.f ? bf16lo(tv[k][e]) : 0.f;
+                const float g1 = fmaf(y1, c1[0], c1[1]) > 0.f ? bf16hi(tv[k][e]) : 0.f;
+                bs1[2 * e] += g0;
+                bs1[2 * e + 1] += g1;
+                bs2[2 * e] = fmaf(g0, (y0 - c0[2]) * c0[3], bs2[2 * e]);
+                bs2[2 * e + 1] = fmaf(g1, (y1 - c1[2]) * c1[3], bs2[2 * e + 1]);
+              }
+          }
+        }
         if (s == 10) frag_store(mp, 0, tv);
       };
       constexpr int LD = 2, KT = MF * KSTEPS;   // one ring of LD+1 activation fragments across all rows
@@ -712,7 +882,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
       }
       if (wave == 0) TRACE(1, sidx);
 #pragma unroll
-      for (int s = 1; s <= 10; ++s) epi(MF - 1, s);
+      for (int s = 1; s <= 11; ++s) epi(MF - 1, s);
     } else {
     if (ch == 0) {
 #pragma unroll
@@ -1120,6 +1290,27 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
     for (int idx = 0; idx < NFR; ++idx) store_frag(idx / NF, idx % NF);
   }
 
+  if constexpr (FUSE) {
+    // BatchNorm sums: every lane's 2 x 8 values through LDS (the x tiles are free after the loop's last barrier), then
+    // thread (st, c) adds the 64 lanes that own channel c in a fixed order
+    float* const scr = reinterpret_cast<float*>(fxt);   // [4 waves][64 lanes][16]
+    static_assert(4 * 64 * 16 * 4 <= 2 * XTB || !FUSE, "the reduction scratch fits the x tiles");
+    float* const mine = scr + (wave * 64 + lane) * 16;
+#pragma unroll
+    for (int j = 0; j < 8; j += 4) {
+      *reinterpret_cast<f32x4*>(mine + j) = f32x4{bs1[j], bs1[j + 1], bs1[j + 2], bs1[j + 3]};
+      *reinterpret_cast<f32x4*>(mine + 8 + j) = f32x4{bs2[j], bs2[j + 1], bs2[j + 2], bs2[j + 3]};
+    }
+    __syncthreads();  // the producer waves join this barrier before they exit
+    if (tid < 64) {
+      const int st = tid >> 5, c = tid & 31;
+      float s = 0.f;
+      for (int w_ = 0; w_ < 4; ++w_)
+        for (int l = 0; l < 16; ++l) s += scr[(w_ * 64 + 4 * l + (c >> 3)) * 16 + st * 8 + (c & 7)];
+      p.bnpart[((size_t)blockIdx.x * 2 + st) * 32 + c] = s;
+    }
+  }
+
   // ---- final statistics ----
   if (STATS) {
     if (WRES) {
@@ -1332,4 +1523,53 @@ int launch_igemm2(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a
     rc = launch_v2<2, 2, 4, 2, false>(p, g, s);
   }
   return rc ? rc : oct_check_launch("igemm2");
+}
+
+// ---- fused backward of a 32 -> 32 layer (oct_conv_backward_fused): dX, dW and the BatchNorm-backward sums of the layer below ----
+// 8-row tiles: next to the two halo tiles of dY the LDS holds the transformed and the raw interior tile of x, double
+// buffered (4 x 16 KB; 151 KB in all).  The 16-row form (130 KB before the x tiles) has no room for them, not even single
+// buffered with the raw tile.
+bool igemm2_fused_plan(const OctWgradDesc* d, ConvPlan* out) {
+  const bool ok = d->dtype == OCT_DT_BF16 && d->depth == 0 && d->taps == 9 && (d->kh == 0 || d->kh == 3) && (d->kw == 0 || d->kw == 3) &&
+                  d->c0 == 32 && d->c1 == 0 && d->cout == 32 && d->xform0 == OCT_XF_AFFINE_RELU && d->dy_mode == OCT_IN_PLAIN &&
+                  d->in_img_shift == 0 && d->dy_img_mul == 0 && d->partials == 0 && d->n > 0 && d->h > 0 && d->w > 0 &&
+                  (d->w % 32) == 0 && (d->h % 8) == 0 && (size_t)d->n * d->h * d->w < (1u << 31);
+  if (!ok) return false;
+  ConvPlan pl = {};
+  pl.path = CONV_IGEMM2;
+  pl.kernel = IG2_TILE;
+  pl.nt = 32; pl.wres = true; pl.nblk = 1; pl.th = 8;
+  const int ntiles = (d->w / 32) * (d->h / 8) * d->n;
+  pl.nitems = ntiles;
+  const int target = ntiles < 256 ? ntiles : 256;   // one persistent workgroup per CU, as the data gradient alone
+  pl.per_wg = (ntiles + target - 1) / target;
+  pl.grid = (ntiles + pl.per_wg - 1) / pl.per_wg;
+  pl.interleave = 0;
+  if (ntiles >= 2 * target) { pl.grid = target; pl.interleave = 1; }
+  pl.stat_rows = pl.grid;   // one row [2][cin] of BatchNorm-backward sums per workgroup: every workgroup of the grid has a tile
+  *out = pl;
+  return true;
+}
+
+int launch_igemm2_fused(const ConvPlan& pl, const OctWgradDesc* d, const OctConvBwdFusedArgs* a, hipStream_t s) {
+  Igemm2Params p = {};
+  p.x0 = (const bf16_t*)a->dy; p.wp = (const bf16_t*)a->wpacked; p.y0 = (bf16_t*)a->dx;
+  p.in_mode = OCT_IN_PLAIN; p.out_mode = OCT_OUT_PLAIN;
+  p.n = d->n; p.h = d->h; p.w = d->w; p.c0 = 32; p.cout = 32;
+  p.tiles_x = d->w / 32; p.tiles_y = d->h / pl.th; p.nblk = 1; p.nitems = pl.nitems; p.per_wg = pl.per_wg;
+  p.interleave = pl.interleave;
+  p.nch = 1; p.nk16 = 2; p.nchc = 1;
+  p.fx = (const bf16_t*)a->x; p.fsc = a->scale; p.fsh = a->shift; p.fmean = a->mean; p.finvstd = a->invstd;
+  p.dwp = a->dwp; p.bnpart = a->partials;
+#ifdef OCT_TRACE
+  p.trace = g_trace;
+#endif
+  constexpr int TH = 8;
+  constexpr int lds = 2 * (TH + 2) * 34 * ig2_pixb<9, 1, true, false>() + (2 * 4 * 2 * 32 + 4 + 2 * 1024) * (int)sizeof(float) + 2 * 4 * 32 * 80 +
+                      1024 * (int)sizeof(float) + 4 * TH * 32 * 64;
+  static_assert(lds <= 160 * 1024, "LDS budget");
+  const auto kern = igemm2_kernel<9, 4, 1, 2, 1, true, false, false, false, false, false, true>;
+  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
+  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), lds, s, p);
+  return oct_check_launch("igemm2 (fused backward)");
 }

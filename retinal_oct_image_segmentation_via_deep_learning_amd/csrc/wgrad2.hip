@@ -47,7 +47,6 @@ extern "C" void oct_debug_set_trace_w2(void* buf) { g_trace_w2 = (unsigned long 
 #endif
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned w2_pack(float a, float b) {
   typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -55,26 +54,6 @@ __device__ __forceinline__ unsigned w2_pack(float a, float b) {
   v[0] = (bf16_t)a;
   v[1] = (bf16_t)b;
   return __builtin_bit_cast(unsigned, v);
-}
-
-// one MFMA operand fragment (8 contraction pixels per lane) through two transposed LDS reads
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base_lo) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo + 4 * 64));  // pixels +4
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// the same with the two reads addressed separately (swizzled tiles: the second read's half can differ per lane)
-__device__ __forceinline__ bf16x8 tr_frag2(const unsigned char* first, const unsigned char* second) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(first));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(second));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(bf16x8, v);
 }
 
 // D3: depth shift of the input tile / image map of an S2D dY (volumetric network) -- compile-time, see igemm2.hip

@@ -174,6 +174,7 @@ class UNetEngine:
         # deterministic = True: weight gradients through the two-stage reduction (OctWgradDesc.partials: per-workgroup slabs
         # summed in order) instead of fp32 atomics -- bit-identical gradients from run to run (OCT_DETERMINISTIC=1 sets it)
         self.deterministic = os.environ.get("OCT_DETERMINISTIC", "0") == "1"
+        self.fused_bwd_off = False   # True: the 32 -> 32 layers keep the separate dW / dX / BatchNorm-reduction launches (parity tests)
         self.debug = None  # set to a dict to capture intermediate gradients (tests / probes)
         self.prof = None   # set to a list: (kind, start_event, end_event) around every MFMA launch
         self.prof_labels = None   # set to a list next to `prof`: (taps, cin, cout, n, h, w, in/dy mode, out mode) per launch
@@ -567,13 +568,44 @@ class UNetEngine:
                 y=rec.y.float().clone())
         return d0, d1
 
+    def _conv_backward_fused(self, r1: ConvRec, r2: ConvRec, dy2, G, accumulate):
+        """Second convolution of a block, 32 -> 32 channels, fed by relu(bn(y1)): dA1, dW2 (queued for unpack) and the
+        BatchNorm-backward partial sums of conv1 from ONE launch (oct_conv_backward_fused).  Returns (dA1, partials), or
+        None where the library says no -- the caller then keeps the separate launches.  The debug path records per-layer
+        tensors and the deterministic mode sums its weight gradients in order: both keep the separate launches too."""
+        src = r2.src
+        if self.fused_bwd_off or self.debug is not None or self.deterministic or src.c1 or src.bn0 is None or src.bn0 is not r1.bn or src.x0 is not r1.y:
+            return None
+        lib = L.lib()
+        n, h, w, cin, cout = r2.n, r2.h, r2.w, src.c0, r2.cout
+        d = L.WgradDesc(self.dt, n, h, w, cin, 0, cout, 9, _xf(src.bn0), L.XF_NONE, L.IN_PLAIN, 0, 0, 0, 0, 0, 0, 0)
+        if not lib.oct_conv_backward_fused_ok(C.byref(d)):   # the library decides (shape, dtype, OCT_DISABLE_V2)
+            return None
+        dev = dy2.device
+        wp = self._pack(r2.wkey, self._P[r2.wkey], L.PACK_CONV_DGRAD, cout, cin)
+        da1 = self._act(n, h, w, cin, dev)
+        dwp = self._dwp_take(9 * cout * cin, dev).view(9, cout, cin)
+        parts = torch.empty((lib.oct_conv_backward_fused_blocks(C.byref(d)), 2, cin), dtype=torch.float32, device=dev)
+        a = L.ConvBwdFusedArgs(L.ptr(r1.y), L.ptr(r1.bn.scale), L.ptr(r1.bn.shift), L.ptr(r1.bn.mean), L.ptr(r1.bn.invstd),
+                               L.ptr(dy2), L.ptr(wp), L.ptr(da1), L.ptr(dwp), L.ptr(parts))
+        ev = self._prof_begin()
+        L.check(lib.oct_conv_backward_fused(C.byref(d), C.byref(a), _stream()), "oct_conv_backward_fused")
+        self._prof_end(ev, "igemm", (9, cout, cin, n, h, w, L.IN_PLAIN, L.OUT_PLAIN))
+        self._unpack(L.PACK_CONV_FPROP, dwp, G[r2.wkey], cout, cin, accumulate)
+        return da1, parts
+
     def _block_backward(self, name, da, dpool, G, accumulate, need_dx=True, partials=None):
         r1, r2 = self._ctx.convs[name]
         for r in (r1, r2):
             if r.cbkey and not accumulate and not r.bn.frozen:
                 G[r.cbkey].zero_()   # a bias in front of a train-mode BatchNorm cancels in (y - mean): zero gradient
         dy2 = self._bn_backward(r2, da, dpool, G, accumulate, partials=partials)
-        da1, _ = self._conv_backward(r2, dy2, G, accumulate)
+        fused = self._conv_backward_fused(r1, r2, dy2, G, accumulate)
+        if fused is not None:
+            # one launch gave dA1, dW2 and the BatchNorm-backward sums of conv1: no weight-gradient pass, no reduction pass
+            da1, parts1 = fused
+        else:
+            (da1, _), parts1 = self._conv_backward(r2, dy2, G, accumulate), None
         first_fused = False
         if not need_dx and r1.src.c1 == 0 and r1.src.bn0 is None:
             # the library decides (shape, dtype, OCT_DISABLE_V2): a host-side copy of that rule would drift
@@ -582,12 +614,12 @@ class UNetEngine:
         if first_fused:
             # first layer: no data gradient, so dY1 has a single consumer -- the weight-gradient kernel
             # applies the BN backward itself and the dY1 tensor is never written
-            da1, coef = self._bn_backward(r1, da1, None, G, accumulate, defer_apply=True)
+            da1, coef = self._bn_backward(r1, da1, None, G, accumulate, partials=parts1, defer_apply=True)
             dwp = self._wgrad(r1.src, da1, r1.cout, 9, r1.n, r1.h, r1.w,
                               fused_apply=(r1.y, coef, r1.bn.scale, r1.bn.shift))
             self._unpack(L.PACK_CONV_FPROP, dwp, G[r1.wkey], r1.cout, 1, accumulate)
             return None, None
-        dy1 = self._bn_backward(r1, da1, None, G, accumulate)
+        dy1 = self._bn_backward(r1, da1, None, G, accumulate, partials=parts1)
         return self._conv_backward(r1, dy1, G, accumulate, need_dx=need_dx)
 
     def backward_stages(self):

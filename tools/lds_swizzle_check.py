@@ -54,6 +54,15 @@ def wgrad2_tr(w16, swz, tx, h, second, LW=34, row=0):
     return f
 
 
+def fused_tr(pitch, col0, second):
+    """transposed read of the fused backward (igemm2 FUSE, 32x32x16 form): pixel col0 + 8*(g4>>1) + (li>>2) (+ 4) of a tile row at
+    `pitch` bytes per pixel -- 80 for the dY halo tile (col0 = 16 * half + 2 - tx), 64 for the interior x tile"""
+    def f(l):
+        g4, li = l >> 4, l & 15
+        return (col0 + 8 * (g4 >> 1) + (li >> 2) + (4 if second else 0)) * pitch + (16 * (g4 & 1) + 4 * (li & 3)) * 2
+    return f
+
+
 if __name__ == "__main__":
     for pitch in (80, 96):
         a = [cycles(igemm2_a(pitch, tx, k), G128, 16) for tx in range(3) for k in range(2)]
@@ -64,3 +73,5 @@ if __name__ == "__main__":
     for w16, swz in ((False, False), (True, False), (True, True)):
         r = [cycles(wgrad2_tr(w16, swz, tx, h, s, row=row), G64, 8) for tx in range(3) for h in range(2) for s in (False, True) for row in (0, 1)]
         print(f"wgrad2 transposed reads, 16x16x32={w16} swizzle={swz}: {r}")
+    print("fused backward transposed reads: dY tile (80 B)", [cycles(fused_tr(80, 16 * h + 2 - tx, s), G64, 8) for tx in range(3) for h in range(2) for s in (False, True)],
+          " x tile (64 B)", [cycles(fused_tr(64, 16 * h, s), G64, 8) for h in range(2) for s in (False, True)])
