@@ -436,6 +436,49 @@ int oct_seg_loss_finalize_weighted(const OctHeadDesc* d, const double* loss_part
                                    float w_ce, float w_dice, float dice_eps, float* loss_out,
                                    float* dice_coef, double* wsum_out, void* stream);
 
+/* Binary / multi-label head (library 0.2.2, same OCT_VERSION): `classes` independent sigmoid
+ * channels instead of one softmax.  Logits as above (layout, d->dtype); the target is a uint8 mask
+ * [n,classes,h,w] (NCHW plane order for BOTH logits layouts) with values 0 / 1.
+ *   pos_weight    float [classes] on the device, NULL: 1
+ *   pixel_weight  float [n,h,w] on the device, NULL: 1; one value for every channel of a pixel
+ *   has_ignore / ignore_value (in [2,255])   an element whose target equals it does not count
+ *   omega = valid * pixel_weight
+ *   l     = (1 - t) x + (1 + (pos_weight[c] - 1) t) (log1p(exp(-|x|)) + max(-x, 0))
+ *           (torch's BCEWithLogitsLoss(pos_weight=))
+ *   BCE   = sum omega l / sum omega     over all n*classes*h*w elements
+ *   Dice  = 1 - mean_c (2 I_c + eps) / (P_c + Y_c + eps),  I_c = sum sigmoid(x) t, P_c = sum
+ *           sigmoid(x), Y_c = sum t over the valid elements of channel c, not weighted
+ * A valid target that is neither 0 nor 1 gives a NaN loss; everything ignored gives NaN; an
+ * ignored element gets a gradient of exactly 0 whatever its logit is (NaN included).  The rows
+ * have the layout of oct_seg_loss_forward_weighted's (slot 0 = sum omega*l, slot 1 = sum omega,
+ * then I_c, P_c, Y_c) and oct_seg_loss_finalize_weighted reduces them: [loss, bce, dice], the
+ * Dice backward coefficients and sum omega.  No atomics, fixed order.
+ *   BCE only:  [weight_sum ->] backward(loss_partials = rows) -> finalize_weighted
+ *   with Dice: forward -> finalize_weighted(wsum_out) -> backward(dice_coef)
+ * weight_sum is needed only with a map or ignore_value: without both, sum omega is the element
+ * count and wsum may be NULL.                                                                    */
+/* sum omega from the target and the map alone (target may be NULL without has_ignore);
+ * partials: [oct_seg_loss_blocks] doubles of scratch, wsum: one double                          */
+int oct_bce_loss_weight_sum(const OctHeadDesc* d, const uint8_t* target, const float* pixel_weight,
+                            int has_ignore, int ignore_value, double* partials, double* wsum,
+                            void* stream);
+/* mask (uint8 [n,classes,h,w], may be NULL) = x >= tau, 0 for a NaN logit; loss_partials (may be
+ * NULL, needs target): [oct_seg_loss_blocks][OCT_HEAD_LOSS_SLOTS], the Dice slots zero unless
+ * want_dice.  target == NULL with a mask only is a pure predict.                                 */
+int oct_bce_loss_forward(const OctHeadDesc* d, int layout, const void* logits, const uint8_t* target,
+                         const float* pos_weight, const float* pixel_weight, int has_ignore,
+                         int ignore_value, int want_dice, float tau, uint8_t* mask,
+                         double* loss_partials, void* stream);
+/* dlogits (layout and dtype of the logits) = g * valid * [w_bce (omega / sum omega) (s (1 - t +
+ * pos_weight t) - pos_weight t) + s (1 - s) (A_c t + B_c)], s = sigmoid(x), A / B from dice_coef
+ * (NULL: no Dice term), g = *dloss (NULL: 1), sum omega = *wsum (device double; NULL, allowed
+ * without a map and ignore_value: the element count).  loss_partials (only with dice_coef == NULL,
+ * may be NULL): rows with slots 0 and 1 filled.                                                  */
+int oct_bce_loss_backward(const OctHeadDesc* d, int layout, const void* logits, const uint8_t* target,
+                          const float* pos_weight, const float* pixel_weight, int has_ignore,
+                          int ignore_value, const double* wsum, const float* dice_coef, float w_bce,
+                          const float* dloss, void* dlogits, double* loss_partials, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Layout / dtype helpers and the optimizer
  * ------------------------------------------------------------------------------------------ */

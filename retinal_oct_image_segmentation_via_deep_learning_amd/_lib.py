@@ -164,6 +164,11 @@ SIGNATURES = {
                                                C.c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oct_seg_loss_finalize_weighted": (c_int, [C.POINTER(HeadDesc), c_void_p, c_int, c_float, c_float, c_float, c_void_p,
                                                c_void_p, c_void_p, c_void_p]),
+    "oct_bce_loss_weight_sum": (c_int, [C.POINTER(HeadDesc), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "oct_bce_loss_forward": (c_int, [C.POINTER(HeadDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_float, c_void_p, c_void_p, c_void_p]),
+    "oct_bce_loss_backward": (c_int, [C.POINTER(HeadDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                      c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oct_nchw_to_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "oct_nhwc_to_nchw": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "oct_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_int,

@@ -526,3 +526,274 @@ extern "C" int oct_seg_loss_finalize_weighted(const OctHeadDesc* d, const double
                      d->classes, w_ce, w_dice, dice_eps, loss_out, dice_coef, wsum_out);
   return oct_check_launch("seg_loss_finalize_weighted");
 }
+
+// ---- binary / multi-label head: sigmoid BCE + soft Dice on independent channels -------------------------------------------
+// Every (pixel, channel) element is its own two-class problem: logit x, target t in {0, 1} from a uint8 mask in NCHW plane
+// order (B, C, H, W) whatever the logits' layout -- a lane reads one byte per channel, the lanes of a wave consecutive bytes.
+//   valid = !(has_ignore && t == ignore_value);   omega = valid * pixel_weight[pixel]   (one map value for all channels)
+//   l     = (1 - t) x + (1 + (pos_weight[c] - 1) t) softplus(-x)     torch's BCEWithLogitsLoss(pos_weight=), stable form
+//   BCE   = sum omega l / sum omega;   Dice sums I_c, P_c, Y_c of sigmoid(x) over the valid elements, not weighted
+// Same tiling as above (a workgroup owns 256 consecutive pixels, one per lane, every channel of it) and the same rows:
+// slot 0 = sum omega l, slot 1 = sum omega, then the Dice sums -- seg_finalize_weighted_kernel finalises them unchanged and its
+// dice_coef feeds the backward kernel.  An ignored element enters every sum and the gradient through a select, never through a
+// product, so a NaN logit under it cannot leak.  A valid t outside {0, 1} makes l (and the loss) NaN.
+// OPTS = false: no pos_weight, no map, no ignore_value -- none of them is read and sum omega is the element count.
+struct BceParams {
+  SegParams s;   // logits / layout / rows / dice_coef / dloss / dlogits / w_ce (= w_bce) / pixel_weight / wsum / has_ignore
+  const unsigned char* target; unsigned char* mask; const float* pos_weight;
+  float tau; int ignore_value; int want_dice;
+};
+
+// softplus(-x) and sigmoid(x) from one exp(-|x|).  No contraction here or in the two functions below: the forward and the
+// backward kernel, in both layouts, must give the same bits for the same element.
+__device__ __forceinline__ void bce_terms(float x, float& sp, float& sig) {
+#pragma clang fp contract(off)
+  const float e = expf(-fabsf(x));
+  const float r = 1.f / (1.f + e);
+  sp = log1pf(e) + fmaxf(-x, 0.f);
+  sig = x >= 0.f ? r : e * r;
+}
+
+__device__ __forceinline__ float bce_elem(float x, int t, float pw, float sp) {
+#pragma clang fp contract(off)
+  const float tf = (float)t;
+  const float le = (1.f - tf) * x + (1.f + (pw - 1.f) * tf) * sp;
+  return t <= 1 ? le : __builtin_nanf("");
+}
+
+// g [w_bce k (sig (1 - t + pw t) - pw t) + sig (1 - sig) (A t + B)],  k = omega / sum omega
+__device__ __forceinline__ float bce_grad(int t, float pw, float sig, float wk, float a, float b, float g) {
+#pragma clang fp contract(off)
+  const float tf = (float)t;
+  const float pt = pw * tf;
+  const float gb = sig * ((1.f - tf) + pt) - pt;
+  const float gd = (sig * (1.f - sig)) * (a * tf + b);
+  return (wk * gb + gd) * g;
+}
+
+// the plane offset of a live lane's pixel: element (img, c, off) of a (B, C, H, W) tensor is at base + c * hw
+__device__ __forceinline__ size_t bce_plane_base(const SegParams& s, size_t pix) {
+  const size_t img = pix / s.hw;
+  return img * (size_t)s.classes * s.hw + (pix - img * s.hw);
+}
+
+// mask (may be null): uint8 (B, C, H, W) = x >= tau (a NaN logit gives 0); rows (may be null, need the target)
+template <bool NCHW, typename T, int CMAX, bool OPTS>
+__global__ void __launch_bounds__(SEG_THREADS) bce_fwd_kernel(const BceParams p) {
+  __shared__ __attribute__((aligned(16))) SegStage<T, NCHW ? 1 : CMAX> stage;
+  __shared__ double red[SEG_THREADS / 64][OCT_HEAD_LOSS_SLOTS];
+  const SegParams& s = p.s;
+  const int C = s.classes;
+  const bool dice = p.want_dice != 0;
+  double ws = 0.0;
+  float bce = 0.f, si[CMAX], sp[CMAX], sy[CMAX];
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) { si[c] = 0.f; sp[c] = 0.f; sy[c] = 0.f; }
+  const size_t ntiles = (s.npix + SEG_THREADS - 1) / SEG_THREADS;
+  for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const size_t p0 = tile * SEG_THREADS, pix = p0 + threadIdx.x;
+    const int np = (int)(s.npix - p0 < SEG_THREADS ? s.npix - p0 : SEG_THREADS);
+    float l[CMAX];
+    seg_load<NCHW, T, CMAX>(s, p0, np, stage.v, l);
+    if (threadIdx.x < np) {
+      const size_t base = bce_plane_base(s, pix);
+      float pm = 1.f;
+      if constexpr (OPTS)
+        if (s.loss_partials && s.pixel_weight) pm = s.pixel_weight[pix];
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c) {
+        if (c < C) {
+          const float x = l[c];
+          if (p.mask) p.mask[base + (size_t)c * s.hw] = x >= p.tau ? 1 : 0;
+          if (s.loss_partials) {
+            const int t = p.target[base + (size_t)c * s.hw];
+            bool valid = true;
+            float pw = 1.f;
+            if constexpr (OPTS) {
+              valid = !(s.has_ignore && t == p.ignore_value);
+              if (p.pos_weight) pw = p.pos_weight[c];
+            }
+            float spl, sig;
+            bce_terms(x, spl, sig);
+            const float le = bce_elem(x, t, pw, spl);
+            if (valid) {   // an ignored element adds exactly nothing, whatever its logit is
+              if constexpr (OPTS) { bce = fmaf(pm, le, bce); ws += (double)pm; }
+              else { bce += le; ws += 1.0; }
+              if (dice) {
+                si[c] += t ? sig : 0.f;
+                sp[c] += sig;
+                sy[c] += (float)t;
+              }
+            }
+          }
+        }
+      }
+    }
+    if (!NCHW) __syncthreads();   // the next tile overwrites the stage
+  }
+  if (s.loss_partials)
+    seg_write_row<CMAX, true>(s.loss_partials + (size_t)blockIdx.x * OCT_HEAD_LOSS_SLOTS, bce, si, sp, sy, dice, red, ws);
+}
+
+// dlogits in the logits' layout and dtype, exactly 0 for an ignored element; sum omega = *wsum (device double; null: the
+// element count); rows (only without a Dice term): slots 0 and 1, so the BCE-only step reads the logits once
+template <bool NCHW, typename T, int CMAX, bool OPTS>
+__global__ void __launch_bounds__(SEG_THREADS) bce_bwd_kernel(const BceParams p) {
+  __shared__ __attribute__((aligned(16))) SegStage<T, NCHW ? 1 : CMAX> stage;
+  __shared__ double red[SEG_THREADS / 64][OCT_HEAD_LOSS_SLOTS];
+  const SegParams& s = p.s;
+  const int C = s.classes;
+  const float g = s.dloss ? *s.dloss : 1.f;
+  const float inv_n = (float)(1.0 / (s.wsum ? *s.wsum : (double)s.npix * (double)C));
+  double ws = 0.0;
+  float bce = 0.f;
+  T* out = reinterpret_cast<T*>(s.dlogits);
+  const size_t ntiles = (s.npix + SEG_THREADS - 1) / SEG_THREADS;
+  for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const size_t p0 = tile * SEG_THREADS, pix = p0 + threadIdx.x;
+    const int np = (int)(s.npix - p0 < SEG_THREADS ? s.npix - p0 : SEG_THREADS);
+    float l[CMAX];
+    seg_load<NCHW, T, CMAX>(s, p0, np, stage.v, l);
+    const bool live = threadIdx.x < np;
+    if (!NCHW) __syncthreads();   // every lane has read its logits from the stage
+    if (live) {
+      const size_t base = bce_plane_base(s, pix);
+      float pm = 1.f;
+      if constexpr (OPTS)
+        if (s.pixel_weight) pm = s.pixel_weight[pix];
+      const float wk = s.w_ce * (pm * inv_n);
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c) {
+        if (c < C) {
+          const float x = l[c];
+          const int t = p.target[base + (size_t)c * s.hw];
+          bool valid = true;
+          float pw = 1.f;
+          if constexpr (OPTS) {
+            valid = !(s.has_ignore && t == p.ignore_value);
+            if (p.pos_weight) pw = p.pos_weight[c];
+          }
+          const float a = s.dice_coef ? s.dice_coef[c] : 0.f, b = s.dice_coef ? s.dice_coef[OCT_MAX_CLASSES + c] : 0.f;
+          float spl, sig;
+          bce_terms(x, spl, sig);
+          const float dl = valid ? bce_grad(t, pw, sig, wk, a, b, g) : 0.f;
+          if (s.loss_partials && valid) {
+            const float le = bce_elem(x, t, pw, spl);
+            if constexpr (OPTS) { bce = fmaf(pm, le, bce); ws += (double)pm; }
+            else { bce += le; ws += 1.0; }
+          }
+          if (NCHW) reinterpret_cast<float*>(s.dlogits)[base + (size_t)c * s.hw] = dl;
+          else stage.v[threadIdx.x * C + c] = from_f32<T>(dl);
+        }
+      }
+    }
+    if (!NCHW) {
+      __syncthreads();
+      stage_copy<T>(out + p0 * C, stage.v, np * C, s.vec_out);
+      __syncthreads();   // the next tile overwrites the stage
+    }
+  }
+  if (s.loss_partials) {
+    float z[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) z[c] = 0.f;
+    seg_write_row<CMAX, true>(s.loss_partials + (size_t)blockIdx.x * OCT_HEAD_LOSS_SLOTS, bce, z, z, z, false, red, ws);
+  }
+}
+
+// sum(omega) from the targets and the map alone, in the order the rows' slot 1 is summed: per-lane fp64 sums over the
+// channels of each pixel, wave, workgroup, one partial per workgroup.  Without ignore_value the targets are not read.
+__global__ void __launch_bounds__(SEG_THREADS) bce_wsum_kernel(const BceParams p) {
+  __shared__ double red[SEG_THREADS / 64];
+  const SegParams& s = p.s;
+  double ws = 0.0;
+  const size_t ntiles = (s.npix + SEG_THREADS - 1) / SEG_THREADS;
+  for (size_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const size_t pix = tile * SEG_THREADS + threadIdx.x;
+    if (pix < s.npix) {
+      const size_t base = bce_plane_base(s, pix);
+      const double pm = s.pixel_weight ? (double)s.pixel_weight[pix] : 1.0;
+      for (int c = 0; c < s.classes; ++c) {
+        const bool valid = !(s.has_ignore && (int)p.target[base + (size_t)c * s.hw] == p.ignore_value);
+        if (valid) ws += pm;
+      }
+    }
+  }
+  ws = wave_sum(ws);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ws;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0;
+    for (int wv = 0; wv < SEG_THREADS / 64; ++wv) a += red[wv];
+    s.wsum_partials[blockIdx.x] = a;
+  }
+}
+
+static int bce_check(const OctHeadDesc* d, int layout, int has_ignore, int ignore_value, const char* who) {
+  int rc = seg_check(d, layout, who);
+  if (rc) return rc;
+  OCT_CHECK(!has_ignore || (ignore_value >= 2 && ignore_value <= 255), "%s: ignore_value %d not in [2,255]", who, ignore_value);
+  return OCT_OK;
+}
+
+static BceParams bce_params(const OctHeadDesc* d, const void* logits, const uint8_t* target, const float* pos_weight,
+                            const float* pixel_weight, int has_ignore, int ignore_value) {
+  BceParams p = {};
+  p.s = seg_params(d, logits);
+  p.s.pixel_weight = pixel_weight; p.s.has_ignore = has_ignore != 0;
+  p.target = target; p.pos_weight = pos_weight; p.ignore_value = ignore_value;
+  return p;
+}
+
+extern "C" int oct_bce_loss_weight_sum(const OctHeadDesc* d, const uint8_t* target, const float* pixel_weight, int has_ignore,
+                                       int ignore_value, double* partials, double* wsum, void* stream) {
+  int rc = bce_check(d, OCT_SEG_NHWC, has_ignore, ignore_value, "oct_bce_loss_weight_sum");
+  if (rc) return rc;
+  OCT_CHECK(partials && wsum, "oct_bce_loss_weight_sum: null pointer (partials and wsum are required)");
+  OCT_CHECK(target || !has_ignore, "oct_bce_loss_weight_sum: null pointer (ignore_value needs the target)");
+  BceParams p = bce_params(d, nullptr, target, nullptr, pixel_weight, has_ignore, ignore_value);
+  p.s.wsum_partials = partials;
+  const int grid = oct_seg_loss_blocks(p.s.npix, d->classes);
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(bce_wsum_kernel, dim3(grid), dim3(SEG_THREADS), 0, s, p);
+  hipLaunchKernelGGL(seg_wsum_reduce_kernel, dim3(1), dim3(64), 0, s, partials, grid, wsum);
+  return oct_check_launch("bce_loss_weight_sum");
+}
+
+extern "C" int oct_bce_loss_forward(const OctHeadDesc* d, int layout, const void* logits, const uint8_t* target,
+                                    const float* pos_weight, const float* pixel_weight, int has_ignore, int ignore_value,
+                                    int want_dice, float tau, uint8_t* mask, double* loss_partials, void* stream) {
+  int rc = bce_check(d, layout, has_ignore, ignore_value, "oct_bce_loss_forward");
+  if (rc) return rc;
+  OCT_CHECK(logits, "oct_bce_loss_forward: null pointer (logits)");
+  OCT_CHECK(mask || loss_partials, "oct_bce_loss_forward: null pointer (neither mask nor loss_partials)");
+  OCT_CHECK(!loss_partials || target, "oct_bce_loss_forward: null pointer (loss partials need a target)");
+  BceParams p = bce_params(d, logits, target, pos_weight, pixel_weight, has_ignore, ignore_value);
+  p.mask = mask; p.tau = tau; p.want_dice = want_dice; p.s.loss_partials = loss_partials;
+  const int grid = oct_seg_loss_blocks(p.s.npix, d->classes);
+  hipStream_t s = as_stream(stream);
+  if (loss_partials && (pos_weight || pixel_weight || has_ignore)) SEG_DISPATCH(bce_fwd_kernel, true, d, layout, grid, s, p);
+  else SEG_DISPATCH(bce_fwd_kernel, false, d, layout, grid, s, p);
+  return oct_check_launch("bce_loss_fwd");
+}
+
+extern "C" int oct_bce_loss_backward(const OctHeadDesc* d, int layout, const void* logits, const uint8_t* target,
+                                     const float* pos_weight, const float* pixel_weight, int has_ignore, int ignore_value,
+                                     const double* wsum, const float* dice_coef, float w_bce, const float* dloss,
+                                     void* dlogits, double* loss_partials, void* stream) {
+  int rc = bce_check(d, layout, has_ignore, ignore_value, "oct_bce_loss_backward");
+  if (rc) return rc;
+  OCT_CHECK(logits && target && dlogits, "oct_bce_loss_backward: null pointer (logits, target and dlogits are required)");
+  OCT_CHECK(!(loss_partials && dice_coef), "oct_bce_loss_backward: BCE rows come from the backward only without a Dice term");
+  OCT_CHECK(wsum || !(pixel_weight || has_ignore),
+            "oct_bce_loss_backward: null pointer (a pixel_weight map or ignore_value needs wsum)");
+  BceParams p = bce_params(d, logits, target, pos_weight, pixel_weight, has_ignore, ignore_value);
+  p.s.dice_coef = dice_coef; p.s.w_ce = w_bce; p.s.dloss = dloss; p.s.dlogits = dlogits;
+  p.s.loss_partials = loss_partials; p.s.wsum = wsum;
+  p.s.vec_out = ((uintptr_t)dlogits & 15) == 0;
+  const int grid = oct_seg_loss_blocks(p.s.npix, d->classes);
+  hipStream_t s = as_stream(stream);
+  if (pos_weight || pixel_weight || has_ignore) SEG_DISPATCH(bce_bwd_kernel, true, d, layout, grid, s, p);
+  else SEG_DISPATCH(bce_bwd_kernel, false, d, layout, grid, s, p);
+  return oct_check_launch("bce_loss_bwd");
+}

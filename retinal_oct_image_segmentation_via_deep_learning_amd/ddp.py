@@ -208,14 +208,30 @@ class DataParallelTrainer:
     weighted loss of losses.cross_entropy_dice.  Each rank normalises by the sum of ITS OWN weights, and the gradients are
     then averaged over ranks: the same as per-rank mean losses under stock DDP, and like those not the loss of the
     global batch when the ranks' weight sums differ.  The weighted loss is not captured: use_graph=True refuses
-    class_weight / ignore_index at construction and a pixel_weight in step()."""
+    class_weight / ignore_index at construction and a pixel_weight in step().
+
+    loss="binary" (default "ce"): the sigmoid BCE + soft-Dice head of losses.binary_cross_entropy_dice -- step(x, target,
+    pixel_weight=None) calls model.forward_backward_binary with w_ce as the BCE weight, pos_weight= and ignore_value=
+    (constants of the run; class_weight / ignore_index belong to loss="ce").  The per-rank normalisation note above applies
+    unchanged.  The binary step is not captured: use_graph=True refuses loss="binary".  Pass everything after `model` by
+    keyword: loss / pos_weight / ignore_value sit in front of class_weight / ignore_index, which stay the last two."""
 
     def __init__(self, model, lr=0.01, momentum=0.9, weight_decay=0.0, w_ce=1.0, w_dice=0.0, use_graph=False,
                  graph_warmup=2, bucket_cap_bytes=3 << 20, always_communicate=False, optimizer="sgd", betas=(0.9, 0.999),
-                 eps=1e-8, max_grad_norm=None, no_decay=None, class_weight=None, ignore_index=None):
+                 eps=1e-8, max_grad_norm=None, no_decay=None, loss="ce", pos_weight=None, ignore_value=None, class_weight=None,
+                 ignore_index=None):
         from .optim import FusedAdam, FusedAdamW, FusedSGD
         if optimizer not in ("sgd", "adam", "adamw"):
             raise ValueError(f"optimizer={optimizer!r}: one of 'sgd', 'adam', 'adamw'")
+        if loss not in ("ce", "binary"):
+            raise ValueError(f"loss={loss!r}: one of 'ce', 'binary'")
+        if loss == "binary" and use_graph:
+            raise NotImplementedError("use_graph=True captures the unweighted fused step only: loss='binary' needs "
+                                      "use_graph=False")
+        if loss == "binary" and (class_weight is not None or ignore_index is not None):
+            raise ValueError("loss='binary' takes pos_weight / ignore_value; class_weight / ignore_index belong to loss='ce'")
+        if loss == "ce" and (pos_weight is not None or ignore_value is not None):
+            raise ValueError("pos_weight / ignore_value belong to loss='binary'")
         staged = hasattr(model, "_engine")
         if use_graph and (class_weight is not None or ignore_index is not None):
             raise NotImplementedError("use_graph=True captures the unweighted fused step only: class_weight / ignore_index "
@@ -241,6 +257,9 @@ class DataParallelTrainer:
             # converted once, here: the per-step call then passes a device tensor
             class_weight = torch.tensor([float(v) for v in class_weight], dtype=torch.float32, device=self.opt.flat_p.device)
         self.class_weight, self.ignore_index = class_weight, ignore_index
+        if pos_weight is not None and not torch.is_tensor(pos_weight):
+            pos_weight = torch.tensor([float(v) for v in pos_weight], dtype=torch.float32, device=self.opt.flat_p.device)
+        self.loss, self.pos_weight, self.ignore_value = loss, pos_weight, ignore_value
         self.use_graph, self.graph_warmup = use_graph, graph_warmup
         self.graph = None
         self.graph_error = None
@@ -280,9 +299,14 @@ class DataParallelTrainer:
         else:
             hook = self.reducer if (self.reducer.active and not self.use_graph) else None
             self.reducer.begin_step()
-            loss = self.model.forward_backward(x, target, self.w_ce, self.w_dice, stage_hook=hook,
-                                               class_weight=self.class_weight, pixel_weight=pixel_weight,
-                                               ignore_index=self.ignore_index)
+            if self.loss == "binary":
+                loss = self.model.forward_backward_binary(x, target, self.w_ce, self.w_dice, stage_hook=hook,
+                                                          pos_weight=self.pos_weight, pixel_weight=pixel_weight,
+                                                          ignore_value=self.ignore_value)
+            else:
+                loss = self.model.forward_backward(x, target, self.w_ce, self.w_dice, stage_hook=hook,
+                                                   class_weight=self.class_weight, pixel_weight=pixel_weight,
+                                                   ignore_index=self.ignore_index)
             self._eager_steps += 1
         scale = self.reducer.finish()       # launches whatever backward did not, then joins the streams
         self.opt.step(grad_scale=scale)

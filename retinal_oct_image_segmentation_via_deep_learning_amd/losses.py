@@ -15,6 +15,12 @@ unweighted one, and a CE-only step still reads the logits once.  With all three 
   SegLossMixin                             forward_backward / loss / predict for the networks that return logits
                                            (U_Net, AttU_Net, AttU_Net4, MGUNet, MGUNet_2, ReLayNet), on the NHWC logits the
                                            network writes: no NCHW copy, no ATen softmax / NLL
+
+Binary / multi-label head (the oct_bce_loss_* kernels): C independent sigmoid channels against a uint8 mask (B, C, H, W).
+  valid = t != ignore_value,  omega = valid * pixel_weight[pixel],  l = BCEWithLogits(x, t, pos_weight[c])
+  BCE = sum omega l / sum omega over all B C H W elements,  Dice as above with p = sigmoid(x) over the valid elements
+  binary_cross_entropy_dice(logits, target, ...)  with w_dice == 0 a drop-in for F.binary_cross_entropy_with_logits
+  SegLossMixin.forward_backward_binary / loss_binary / predict_mask   the same three contracts on the sigmoid head
 """
 from __future__ import annotations
 
@@ -252,6 +258,174 @@ def loss_only(h, target, w_ce, w_dice, dice_eps, opt):
     return h.finalize(part, w_ce, w_dice, dice_eps)[0]
 
 
+# ---- binary / multi-label head: sigmoid BCE + soft Dice (oct_bce_loss_*) ---------------------------------------------------
+def _binary_target(target, n, c, h, w, device):
+    """uint8 view of a uint8 / bool mask of the logits' shape (B, C, H, W); (B, H, W) is accepted for one channel"""
+    shapes = ((n, c, h, w), (n, h, w)) if c == 1 else ((n, c, h, w),)
+    if not torch.is_tensor(target) or target.dtype not in (torch.uint8, torch.bool) or tuple(target.shape) not in shapes:
+        raise RuntimeError(f"target must be uint8 or bool of shape {(n, c, h, w)}, got "
+                           f"{getattr(target, 'dtype', type(target).__name__)} {tuple(getattr(target, 'shape', ()))}")
+    if target.device != torch.device(device):
+        raise RuntimeError(f"target is on {target.device}, logits on {device}")
+    t = target.detach().contiguous()
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def _binary_options(pos_weight, pixel_weight, ignore_value, n, h, w, classes, device):
+    """The three options of the binary loss, checked against the logits' geometry before anything is launched: None when
+    all are absent, else (pos_weight | None, pixel_weight | None, has_ignore, ignore_value) with the weights as contiguous
+    fp32 tensors on `device`.  A sequence of floats is converted here, once per call."""
+    if pos_weight is None and pixel_weight is None and ignore_value is None:
+        return None
+    device = torch.device(device)
+    if ignore_value is not None and (isinstance(ignore_value, bool) or not isinstance(ignore_value, int)):
+        raise TypeError(f"ignore_value must be an int or None, got {type(ignore_value).__name__} {ignore_value!r}")
+    if ignore_value is not None and not 2 <= ignore_value <= 255:
+        raise ValueError(f"ignore_value {ignore_value} is not in [2, 255] (0 and 1 are the mask's own values)")
+    if pos_weight is not None:
+        if not torch.is_tensor(pos_weight):
+            vals = [float(v) for v in pos_weight]
+            if len(vals) != classes:
+                raise RuntimeError(f"pos_weight must have {classes} entries (one per channel), got {len(vals)}")
+            pos_weight = torch.tensor(vals, dtype=torch.float32, device=device)
+        if pos_weight.dtype != torch.float32:
+            raise RuntimeError(f"pos_weight must be fp32, got {pos_weight.dtype}")
+        if tuple(pos_weight.shape) != (classes,):
+            raise RuntimeError(f"pos_weight must have {classes} entries (one per channel), got shape {tuple(pos_weight.shape)}")
+        if pos_weight.device != device:
+            raise RuntimeError(f"pos_weight is on {pos_weight.device}, logits on {device}")
+        pos_weight = pos_weight.detach().contiguous()
+    if pixel_weight is not None:
+        if not torch.is_tensor(pixel_weight) or pixel_weight.dtype != torch.float32:
+            raise RuntimeError(f"pixel_weight must be an fp32 tensor, got {getattr(pixel_weight, 'dtype', type(pixel_weight).__name__)}")
+        if tuple(pixel_weight.shape) != (n, h, w):
+            raise RuntimeError(f"pixel_weight must have shape {(n, h, w)}, got {tuple(pixel_weight.shape)}")
+        if pixel_weight.device != device:
+            raise RuntimeError(f"pixel_weight is on {pixel_weight.device}, logits on {device}")
+        pixel_weight = pixel_weight.detach().contiguous()
+    return pos_weight, pixel_weight, int(ignore_value is not None), int(ignore_value or 0)
+
+
+def mask_threshold(threshold) -> float:
+    """tau = float32(log(threshold / (1 - threshold))): sigmoid(x) >= threshold is x >= tau; 0 at 0.5"""
+    import math
+    import struct
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 < threshold < 1.0:
+        raise ValueError(f"threshold must lie in (0, 1), got {threshold!r}")
+    return struct.unpack("f", struct.pack("f", math.log(threshold / (1.0 - threshold))))[0]
+
+
+class _BinaryLoss(_Loss):
+    """The launch plan of _Loss on the sigmoid head; opt: _binary_options(...) or None.  The rows have the weighted CE
+    rows' layout, so finalize_weighted reduces them."""
+
+    @staticmethod
+    def _opt(opt):
+        return opt if opt is not None else (None, None, 0, 0)
+
+    @staticmethod
+    def needs_wsum(opt):
+        """sum omega is the element count unless a map or ignore_value is there"""
+        return opt is not None and (opt[1] is not None or opt[2] != 0)
+
+    def binary_weight_sum(self, target, opt):
+        scratch = torch.empty(self.blocks + 1, dtype=torch.float64, device=self.dev)
+        _, pm, has_ig, ig = opt
+        L.check(L.lib().oct_bce_loss_weight_sum(C.byref(self.desc), target.data_ptr(), L.ptr(pm), has_ig, ig, scratch.data_ptr(),
+                                                scratch[self.blocks:].data_ptr(), _stream()), "oct_bce_loss_weight_sum")
+        return scratch[self.blocks:]
+
+    def binary_forward(self, target, opt, want_dice):
+        part = self.partials()
+        pw, pm, has_ig, ig = self._opt(opt)
+        L.check(L.lib().oct_bce_loss_forward(C.byref(self.desc), self.layout, self.logits.data_ptr(), target.data_ptr(), L.ptr(pw),
+                                             L.ptr(pm), has_ig, ig, int(want_dice), 0.0, None, part.data_ptr(), _stream()),
+                "oct_bce_loss_forward")
+        return part
+
+    def binary_mask(self, tau):
+        """uint8 (B, C, H, W) = logits >= tau"""
+        mask = torch.empty((self.n, self.c, self.h, self.w), dtype=torch.uint8, device=self.dev)
+        L.check(L.lib().oct_bce_loss_forward(C.byref(self.desc), self.layout, self.logits.data_ptr(), None, None, None, 0, 0, 0,
+                                             float(tau), mask.data_ptr(), None, _stream()), "oct_bce_loss_forward")
+        return mask
+
+    def binary_backward(self, target, opt, wsum, dice_coef, w_bce, dloss=None, part=None):
+        dl = torch.empty_like(self.logits)
+        pw, pm, has_ig, ig = self._opt(opt)
+        L.check(L.lib().oct_bce_loss_backward(C.byref(self.desc), self.layout, self.logits.data_ptr(), target.data_ptr(), L.ptr(pw),
+                                              L.ptr(pm), has_ig, ig, L.ptr(wsum), L.ptr(dice_coef), float(w_bce), L.ptr(dloss),
+                                              dl.data_ptr(), L.ptr(part), _stream()), "oct_bce_loss_backward")
+        return dl
+
+
+def binary_loss_and_dlogits(logits, target, w_bce=1.0, w_dice=0.0, dice_eps=1e-7, pos_weight=None, pixel_weight=None,
+                            ignore_value=None, layout=L.SEG_NHWC):
+    """Training head on NHWC logits (or NCHW fp32 ones with layout=SEG_NCHW): ([loss, bce, dice], dlogits).  Without a Dice
+    term the backward pass also writes the BCE rows (the logits are read once; the Dice entry is then 0), after a pass over
+    the targets and the map for sum omega when a map or ignore_value is there; with one, forward rows -> finalize (which
+    leaves sum omega on the device) -> backward."""
+    h = _BinaryLoss(logits, layout)
+    t = _binary_target(target, h.n, h.c, h.h, h.w, h.dev)
+    opt = _binary_options(pos_weight, pixel_weight, ignore_value, h.n, h.h, h.w, h.c, h.dev)
+    return binary_step(h, t, opt, w_bce, w_dice, dice_eps)
+
+
+def binary_step(h, t, opt, w_bce, w_dice, dice_eps):
+    """binary_loss_and_dlogits on a _BinaryLoss plan with a target and options that are already checked (_binary_target,
+    _binary_options): the networks check them before their forward pass and come here after it"""
+    if w_dice == 0.0:
+        wsum = h.binary_weight_sum(t, opt) if h.needs_wsum(opt) else None
+        part = h.partials()
+        dl = h.binary_backward(t, opt, wsum, None, w_bce, part=part)
+        return h.finalize_weighted(part, w_bce, w_dice, dice_eps)[0], dl
+    out, coef, wsum = h.finalize_weighted(h.binary_forward(t, opt, True), w_bce, w_dice, dice_eps)
+    return out, h.binary_backward(t, opt, wsum if h.needs_wsum(opt) else None, coef, w_bce)
+
+
+def binary_loss_only(h, target, w_bce, w_dice, dice_eps, opt):
+    """[loss, bce, dice] of a _BinaryLoss plan without a backward pass; target: checked by _binary_target; opt:
+    _binary_options(...) or None"""
+    return h.finalize_weighted(h.binary_forward(target, opt, w_dice != 0.0), w_bce, w_dice, dice_eps)[0]
+
+
+class _BinaryCrossEntropyDice(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, layout, w_bce, w_dice, dice_eps, pos_weight, pixel_weight, ignore_value):
+        h = _BinaryLoss(logits.detach(), layout)
+        t = _binary_target(target, h.n, h.c, h.h, h.w, h.dev)
+        ctx.opt = _binary_options(pos_weight, pixel_weight, ignore_value, h.n, h.h, h.w, h.c, h.dev)
+        out, coef, wsum = h.finalize_weighted(h.binary_forward(t, ctx.opt, w_dice != 0.0), w_bce, w_dice, dice_eps)
+        ctx.h, ctx.t, ctx.w_bce = h, t, w_bce
+        ctx.wsum = wsum if h.needs_wsum(ctx.opt) else None
+        ctx.coef = coef if w_dice != 0.0 else None
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dout):
+        # the upstream gradient stays on the device: the kernel reads it, nothing synchronises
+        g = dout.detach().to(torch.float32).contiguous()
+        dl = ctx.h.binary_backward(ctx.t, ctx.opt, ctx.wsum, ctx.coef, ctx.w_bce, dloss=g)
+        ctx.h = ctx.t = ctx.coef = ctx.opt = ctx.wsum = None
+        return dl, None, None, None, None, None, None, None, None
+
+
+def binary_cross_entropy_dice(logits, target, w_bce=1.0, w_dice=0.0, dice_eps=1e-7, pos_weight=None, pixel_weight=None,
+                              ignore_value=None):
+    """w_bce * BCE + w_dice * soft Dice of NCHW fp32 CUDA logits (B, C, H, W) -- C independent sigmoid channels -- against a
+    uint8 or bool mask of the same shape ((B, H, W) is accepted for C == 1): a 0-d loss that autograd differentiates through
+    the HIP backward kernel.  w_dice == 0 and no options: F.binary_cross_entropy_with_logits(logits, target.float()).
+    A mask value that is neither 0 nor 1 (nor ignore_value) gives a NaN loss; at most 16 channels.
+
+    pos_weight: fp32 device tensor of C entries (or a sequence of floats, converted on every call), torch's
+    BCEWithLogitsLoss(pos_weight=); pixel_weight: fp32 device tensor (B, H, W), one value for all channels of a pixel, a
+    constant of the loss; ignore_value: an int in [2, 255] or None -- a mask element that equals it counts nowhere and gets a
+    gradient of exactly 0.  BCE = sum omega l / sum omega with omega = valid * pixel_weight; the Dice sums run over the valid
+    elements, unweighted.  Everything ignored: NaN."""
+    return _BinaryCrossEntropyDice.apply(logits, target, L.SEG_NCHW, float(w_bce), float(w_dice), float(dice_eps), pos_weight,
+                                         pixel_weight, ignore_value)
+
+
 class SegLossMixin:
     """forward_backward / loss / predict (the contracts of unet._EngineNet) for networks that return logits.  The class
     defines `_logits_nhwc(x)` -- its forward without the final NCHW conversion -- and `_head`, the attribute path of its
@@ -318,3 +492,54 @@ class SegLossMixin:
         model(x).argmax(1)."""
         _check_classes(self._classes())
         return _Loss(self._run_logits(x), L.SEG_NHWC).forward(want_argmax=True)[1]
+
+    # ---- binary / multi-label head ----------------------------------------------------------------------------------------
+    def _binary_options_for(self, x, pos_weight, pixel_weight, ignore_value):
+        if x.dim() != 4:
+            raise RuntimeError(f"expected a 4-D input, got {tuple(x.shape)}")
+        return _binary_options(pos_weight, pixel_weight, ignore_value, x.shape[0], x.shape[2], x.shape[3], self._classes(),
+                               x.device)
+
+    def forward_backward_binary(self, x, target, w_bce=1.0, w_dice=0.0, dice_eps=1e-7, stage_hook=None, pos_weight=None,
+                                pixel_weight=None, ignore_value=None):
+        """forward_backward with the sigmoid head of binary_cross_entropy_dice on the NHWC logits: every output channel is
+        its own mask, target is uint8 / bool (B, C, H, W) (or (B, H, W) for one channel).  Same contract: train mode, `.grad`
+        overwritten in place, returns the device tensor [loss, bce, dice]; stage_hook is accepted and ignored."""
+        if not self.training:
+            raise RuntimeError("forward_backward_binary needs train() mode (batch statistics)")
+        _check_classes(self._classes())
+        opt = self._binary_options_for(x, pos_weight, pixel_weight, ignore_value)
+        target = _binary_target(target, x.shape[0], self._classes(), x.shape[2], x.shape[3], x.device)
+        params = [p for p in self.parameters() if p.requires_grad]
+        with torch.enable_grad():
+            lg = self._run_logits(x)
+        out, dl = binary_step(_BinaryLoss(lg, L.SEG_NHWC), target, opt, w_bce, w_dice, dice_eps)
+        grads = torch.autograd.grad(lg, params, dl, allow_unused=True)
+        for p in params:
+            if p.grad is None:
+                p.grad = torch.empty_like(p)
+        used = [(p.grad, g) for p, g in zip(params, grads) if g is not None]
+        if used:
+            torch._foreach_copy_([d for d, _ in used], [g for _, g in used])
+        unused = [p.grad for p, g in zip(params, grads) if g is None]
+        if unused:
+            torch._foreach_zero_(unused)
+        return out
+
+    @torch.no_grad()
+    def loss_binary(self, x, target, w_bce=1.0, w_dice=0.0, dice_eps=1e-7, pos_weight=None, pixel_weight=None,
+                    ignore_value=None):
+        """[loss, bce, dice] of the current mode's forward pass (no gradients; buffers move as in model(x))."""
+        _check_classes(self._classes())
+        opt = self._binary_options_for(x, pos_weight, pixel_weight, ignore_value)
+        target = _binary_target(target, x.shape[0], self._classes(), x.shape[2], x.shape[3], x.device)
+        h = _BinaryLoss(self._run_logits(x), L.SEG_NHWC)
+        return binary_loss_only(h, target, w_bce, w_dice, dice_eps, opt)
+
+    @torch.no_grad()
+    def predict_mask(self, x, threshold=0.5):
+        """uint8 masks (B, C, H, W) of the current mode's forward: sigmoid(logit) >= threshold, evaluated as
+        logit >= float32(log(threshold / (1 - threshold))) -- model(x) >= that value, exactly."""
+        tau = mask_threshold(threshold)
+        _check_classes(self._classes())
+        return _BinaryLoss(self._run_logits(x), L.SEG_NHWC).binary_mask(tau)

@@ -185,6 +185,62 @@ class _EngineNet(nn.Module):
                                            want_logits=True)
         return lg
 
+    # ---- binary / multi-label head (losses.binary_cross_entropy_dice) -----------------------------------------------------
+    def _binary_args(self, x, target, pos_weight, pixel_weight, ignore_value):
+        """(losses._binary_options | None, uint8 target), checked against the input's geometry before anything is launched"""
+        if not self._weighted_loss:
+            raise NotImplementedError(f"{type(self).__name__}: the binary / multi-label loss is implemented for the 2-D networks "
+                                      "only; the volumetric loss head is the fused softmax one")
+        from .losses import _binary_options, _binary_target, _check_classes
+        if x.dim() != 4:
+            raise RuntimeError(f"expected a 4-D input, got {tuple(x.shape)}")
+        ncls = self._engine.ncls
+        _check_classes(ncls)
+        opt = _binary_options(pos_weight, pixel_weight, ignore_value, x.shape[0], x.shape[2], x.shape[3], ncls, x.device)
+        return opt, _binary_target(target, x.shape[0], ncls, x.shape[2], x.shape[3], x.device)
+
+    @torch.no_grad()
+    def forward_backward_binary(self, x, target, w_bce=1.0, w_dice=0.0, dice_eps=1e-7, stage_hook=None, pos_weight=None,
+                                pixel_weight=None, ignore_value=None):
+        """forward_backward with the sigmoid head: every output channel is its own mask, target is uint8 / bool (B, C, H, W)
+        (or (B, H, W) for one channel).  The route of the weighted CE step: the forward writes NCHW fp32 logits, the
+        oct_bce_loss_* kernels give [loss, bce, dice] and d(loss)/d(logits), and the backward starts from those through the
+        generic 1x1 head kernels.  The loss is on the logits also where forward() returns probabilities (UNet)."""
+        if not self.training:
+            raise RuntimeError("forward_backward_binary needs train() mode (batch statistics)")
+        opt, t = self._binary_args(x, target, pos_weight, pixel_weight, ignore_value)
+        from .losses import _BinaryLoss, binary_step
+        P = self._tensors()
+        ectx, _, _, lg = self._engine.forward(P, x, train=True, want_probs=False, want_logits=True)
+        out, dl = binary_step(_BinaryLoss(lg, L.SEG_NCHW), t, opt, w_bce, w_dice, dice_eps)
+        G = {}
+        for n, p in self.named_parameters():
+            if p.grad is None:
+                p.grad = torch.empty_like(p.data)
+            G[n] = p.grad
+        self._engine.backward(P, ectx, G, dlogits=dl, stage_hook=stage_hook)
+        return out
+
+    @torch.no_grad()
+    def loss_binary(self, x, target, w_bce=1.0, w_dice=0.0, dice_eps=1e-7, pos_weight=None, pixel_weight=None,
+                    ignore_value=None):
+        """[loss, bce, dice] of the current mode's forward pass (no gradients)."""
+        opt, t = self._binary_args(x, target, pos_weight, pixel_weight, ignore_value)
+        from .losses import _BinaryLoss, binary_loss_only
+        _, _, _, lg = self._engine.forward(self._tensors(), x, train=self.training, want_probs=False, want_logits=True)
+        return binary_loss_only(_BinaryLoss(lg, L.SEG_NCHW), t, w_bce, w_dice, dice_eps, opt)
+
+    @torch.no_grad()
+    def predict_mask(self, x, threshold=0.5):
+        """uint8 masks (B, C, H, W) of the current mode's forward: sigmoid(logit) >= threshold, evaluated as
+        model.logits(x) >= float32(log(threshold / (1 - threshold))), exactly."""
+        if not self._weighted_loss:
+            raise NotImplementedError(f"{type(self).__name__}: the binary / multi-label head is implemented for the 2-D networks only")
+        from .losses import _BinaryLoss, _check_classes, mask_threshold
+        tau = mask_threshold(threshold)
+        _check_classes(self._engine.ncls)
+        return _BinaryLoss(self.logits(x), L.SEG_NCHW).binary_mask(tau)
+
 
 class UNet(_EngineNet):
     """SOTAS/{Lesions,Layers}_Segment/YNet_2022 `UNet` (reference :509-602)."""

@@ -13,7 +13,11 @@ CFG_WEIGHTED=1: the weighted loss in the cfg4 pairs and the profile step -- clas
     torch  -- F.cross_entropy(model(x), t, weight=w, ignore_index=k) + torch.optim.SGD
     fused  -- model.forward_backward(x, t, class_weight=w, ignore_index=k) + FusedSGD (oct_seg_loss_*_weighted)
   and, as group "unet" (only when named: CFG_ONLY=unet), UNet(1,8) at the headline shape 32x512x1024: the weighted step, which
-  leaves the fused head, against the unweighted fused-head step of the same build, alternating."""
+  leaves the fused head, against the unweighted fused-head step of the same build, alternating.
+CFG_ONLY=binary (only when named): the binary head, AttU_Net(1,1) 16x496x768 against a random uint8 mask, alternating:
+    torch  -- F.binary_cross_entropy_with_logits(model(x), t.float()) + torch.optim.SGD
+    fused  -- model.forward_backward_binary(x, t) + FusedSGD (oct_bce_loss_* on the NHWC logits)
+  with CFG_PROFILE=1 only the fused binary step, 3 warm-up steps + 1."""
 import os
 import statistics
 import sys
@@ -64,6 +68,25 @@ def stepper(model, x, t, fused, w=None, k=None):
     return step
 
 
+def binary_stepper(model, x, t, fused):
+    model.cuda().train()
+    if fused:
+        opt = FusedSGD(list(model.named_parameters()), lr=0.01, momentum=0.9)
+
+        def step():
+            model.forward_backward_binary(x, t)
+            opt.step()
+    else:
+        opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9)
+        tf = t.float()      # converted once, outside the step: the torch path is not charged for it
+
+        def step():
+            opt.zero_grad(set_to_none=True)
+            F.binary_cross_entropy_with_logits(model(x), tf).backward()
+            opt.step()
+    return step
+
+
 def timed(step, n):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -83,12 +106,12 @@ def run(name, model, x, t):
           f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
 
 
-def pair(name, make, x, t, w=None, k=None):
+def pair(name, make, x, t, w=None, k=None, binary=False):
     """the torch-CE path and the fused path of two identically seeded models, timed in alternating rounds"""
     torch.manual_seed(0)
-    st_torch = stepper(make(), x, t, False, w, k)
+    st_torch = binary_stepper(make(), x, t, False) if binary else stepper(make(), x, t, False, w, k)
     torch.manual_seed(0)
-    st_fused = stepper(make(), x, t, True, w, k)
+    st_fused = binary_stepper(make(), x, t, True) if binary else stepper(make(), x, t, True, w, k)
     for _ in range(WARMUP):
         st_torch()
         st_fused()
@@ -98,13 +121,27 @@ def pair(name, make, x, t, w=None, k=None):
         ms["fused"].append(timed(st_fused, steps) * 1e3)
     a, b = statistics.median(ms["torch"]), statistics.median(ms["fused"])
     tag = "weighted " if w is not None else ""
-    print(f"{name}: torch {tag}CE + SGD {a:.2f} ms/step, {tag}forward_backward + FusedSGD {b:.2f} ms/step "
+    lname, fname = ("BCE", "forward_backward_binary") if binary else ("CE", "forward_backward")
+    print(f"{name}: torch {tag}{lname} + SGD {a:.2f} ms/step, {tag}{fname} + FusedSGD {b:.2f} ms/step "
           f"({a - b:+.2f} ms, {a / b:.3f}x; medians of {rounds} rounds x {steps} steps; "
           f"rounds torch {['%.2f' % v for v in ms['torch']]} fused {['%.2f' % v for v in ms['fused']]})", flush=True)
 
 
 ONLY = os.environ.get("CFG_ONLY", "")
 torch.manual_seed(0)
+if ONLY == "binary":
+    x = torch.randn(16, 1, 496, 768, generator=g).cuda()
+    t = (torch.rand(16, 1, 496, 768, generator=g) < 0.3).to(torch.uint8).cuda()
+    if os.environ.get("CFG_PROFILE"):
+        torch.manual_seed(0)
+        step = binary_stepper(AttU_Net(1, 1), x, t, True)
+        for _ in range(4):
+            step()
+        torch.cuda.synchronize()
+        print("binary fused: 4 steps done")
+    else:
+        pair("binary AttU_Net(1,1) 16x496x768", lambda: AttU_Net(1, 1), x, t, binary=True)
+    sys.exit(0)
 if os.environ.get("CFG_PROFILE"):
     x = torch.randn(16, 1, 496, 768, generator=g).cuda()
     t = torch.randint(0, 3, (16, 496, 768), generator=g).cuda()
