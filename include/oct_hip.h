@@ -648,6 +648,41 @@ int oct_sqdiff_sum(const void* y_true, const void* y_pred, int elem, size_t n, d
 int oct_column_absdiff_sum(const void* y_true, const void* y_pred, int elem, int unsigned_wrap, size_t rows,
                            size_t cols, double* out, void* stream);
 
+/* Streaming segmentation evaluator (library 0.2.2, same OCT_VERSION): ONE launch per batch ADDS the C x C confusion
+ * matrix and the per-layer thickness error of a (target, prediction) pair to a device-resident state; nothing is read
+ * back, so a validation loop synchronises once, when it reads the state.
+ *   target  class map [images][h][w], uint8 (target_elem 0) or int64 (target_elem 2) -- the element codes above
+ *   pred    pred_kind OCT_EVAL_PRED_U8 / _I64: a class map of the same shape;
+ *           OCT_EVAL_PRED_NHWC_BF16 / _NHWC_F32: logits [images][h][w][classes]; OCT_EVAL_PRED_NCHW_F32: logits
+ *           [images][classes][h][w].  p = arg-max over the channels with the rule of oct_seg_loss_forward's arg-max
+ *           (first maximum wins, the first NaN beats everything), so p equals what model.predict writes
+ *   state   int64[classes*classes + classes + 4], zeroed ONCE by the caller (hipMemsetAsync), C = classes:
+ *           [t*C + p]          cm         pixels with label t predicted as p
+ *           [C*C + c]          thick_abs  sum over images b and columns x of |T - P|, T = #{y : valid, t == c},
+ *                                         P = #{y : valid, p == c}: the thickness axis is h (np.sum(mask, axis=0) of
+ *                                         Biomarker_based_metrics.thickness_difference on an h x w mask)
+ *           [C*C + C]          columns    += images * w per call
+ *           [C*C + C + 1]      ignored    pixels with has_ignore and t == ignore_index; counted here and nowhere else
+ *           [C*C + C + 2]      invalid    pixels not ignored whose t or p lies outside [0, C); here and nowhere else
+ *           [C*C + C + 3]      updates    += 1 per call
+ * A pixel that is neither ignored nor invalid is "valid".  No label indexes anything before it is range-checked.
+ * Any h, w >= 1 and ANY base alignment of target / pred are accepted (the class maps are read element-wise, logits take
+ * 16-byte loads only where base and row pitch allow them); images * h * w < 2^31, 1 <= classes <= 16.               */
+#define OCT_EVAL_PRED_U8 0
+#define OCT_EVAL_PRED_I64 1
+#define OCT_EVAL_PRED_NHWC_BF16 2
+#define OCT_EVAL_PRED_NHWC_F32 3
+#define OCT_EVAL_PRED_NCHW_F32 4
+#define OCT_EVAL_STATE_EXTRA 4 /* columns, ignored, invalid, updates */
+typedef struct {
+  int images, h, w, classes; /* images = product of all leading dims; 1 <= classes <= 16 */
+  int target_elem;           /* 0 uint8, 2 int64 */
+  int pred_kind;             /* OCT_EVAL_PRED_* */
+  int has_ignore;
+  int64_t ignore_index;
+} OctSegEvalDesc;
+int oct_seg_eval_update(const OctSegEvalDesc* d, const void* target, const void* pred, int64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

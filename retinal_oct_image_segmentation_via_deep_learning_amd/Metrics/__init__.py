@@ -42,3 +42,27 @@ def evaluate(y_true, y_pred, classes=None):
     res = {k: np.array([d[k] for d in per], dtype=np.float64) for k in per[0]}
     res["counts"] = np.array(rows, dtype=np.int64)
     return res
+
+
+def confusion_matrix(y_true, y_pred, classes, ignore_index=None):
+    """int64 [classes, classes] array, entry [t][p] = pixels with label t predicted as p, of two integer class maps (arrays or
+    tensors of one shape): one launch of the streaming evaluator's kernel (evaluation.SegEvaluator, which also accumulates
+    over batches without reading anything back).  Pixels with y_true == ignore_index and labels outside [0, classes) are
+    left out."""
+    import torch
+
+    from ..evaluation import SegEvaluator
+    ev = SegEvaluator(int(classes) if not isinstance(classes, bool) else classes, ignore_index)
+    maps = []
+    for a in (y_true, y_pred):
+        if not torch.is_tensor(a):
+            a = np.asarray(a)
+            if a.dtype.kind not in "iub":
+                raise TypeError(f"class maps must be integer arrays, got {a.dtype}")
+            a = torch.from_numpy(np.ascontiguousarray(a if a.dtype in (np.uint8, np.bool_) else a.astype(np.int64)))
+        maps.append(a)
+    dev = next((a.device for a in maps if a.is_cuda), torch.device("cuda"))
+    yt, yp = (a.to(dev) for a in maps)
+    if yt.dim() < 2:   # a flat list of labels: one row
+        yt, yp = yt.reshape(1, -1), yp.reshape(1, -1)
+    return ev.update(yt, yp).compute()["confusion"]

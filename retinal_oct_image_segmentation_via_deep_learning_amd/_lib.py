@@ -73,6 +73,15 @@ class HeadDesc(C.Structure):
     _fields_ = [(k, c_int) for k in ("dtype", "n", "h", "w", "feat", "classes")]
 
 
+class SegEvalDesc(C.Structure):      # struct OctSegEvalDesc
+    _fields_ = [(k, c_int) for k in ("images", "h", "w", "classes", "target_elem", "pred_kind", "has_ignore")] + \
+               [("ignore_index", C.c_int64)]
+
+
+EVAL_PRED_U8, EVAL_PRED_I64, EVAL_PRED_NHWC_BF16, EVAL_PRED_NHWC_F32, EVAL_PRED_NCHW_F32 = range(5)   # OCT_EVAL_PRED_*
+EVAL_STATE_EXTRA = 4   # columns, ignored, invalid, updates behind cm [C*C] and thick_abs [C]
+
+
 # name -> (restype, argtypes).  Every symbol of include/oct_hip.h is listed here;
 # tests/test_abi.py checks the two stay in sync.
 SIGNATURES = {
@@ -198,6 +207,7 @@ SIGNATURES = {
     "oct_class_confusion_counts": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
     "oct_sqdiff_sum": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_void_p]),
     "oct_column_absdiff_sum": (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_void_p]),
+    "oct_seg_eval_update": (c_int, [C.POINTER(SegEvalDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
