@@ -683,6 +683,38 @@ typedef struct {
 } OctSegEvalDesc;
 int oct_seg_eval_update(const OctSegEvalDesc* d, const void* target, const void* pred, int64_t* state, void* stream);
 
+/* Contour metrics (library 0.2.2, same OCT_VERSION): the exact integers behind Hausdorff, HD95 and ASSD of every class of a
+ * (target, prediction) pair of class maps [images][h][w], uint8 (elem 0) or int64 (elem 2) each.
+ * Contour points of a mask M: the midpoints of the in-image pairs of 4-adjacent pixels with exactly one pixel in M (the
+ * vertices of marching squares at level 0.5); none along the image border.  M_c = {label == c}; a pixel whose TARGET equals
+ * ignore_index is outside the image in both maps (a pair that touches it yields no point); labels outside [0, classes)
+ * belong to no class.  In doubled coordinates (2y, 2x+1) / (2y+1, 2x) every point is integral: D2 = squared distance there
+ * (true distance sqrt(D2) / 2 pixels), D2 < 2^31 because h, w <= 16384.
+ *   records  int64 [images][classes][2][5], WRITTEN (not accumulated).  Direction 0: from every point of pred to the nearest
+ *            point of target; direction 1 the reverse.  Per (image, class, direction):
+ *            [0] n       source points
+ *            [1] max_d2  largest D2
+ *            [2] lo_d2   the D2 of rank lo = (19 * (n - 1)) / 20 (0-based, ascending)
+ *            [3] hi_d2   the D2 of rank min(lo + 1, n - 1)
+ *            [4] sum_q   sum of floor(2^16 * sqrt(D2)), every term exact
+ *            n == 0 or no point on the other side: [1..4] are 0.
+ *   workspace  oct_contour_workspace_bytes(d) bytes on the device, 16-byte aligned, contents irrelevant before and after:
+ *            with Hd = 2h-1, Wd = 2w-1, S = Hd*Wd, G = ceil(Hd/64), each term rounded up to 256 bytes:
+ *            2*images*h*w + 4*images*classes*S + 16*images*classes*G*Wd + 16*images*(S/2) + 8*images*classes
+ *            + 32*images*classes + 4096*images*classes.  0 for a descriptor that oct_contour_update rejects.
+ * A fixed sequence of launches on `stream`; no allocation, no host synchronisation, integer atomics only: two runs give the
+ * same bits.  images * h * w < 2^31.                                                                                   */
+typedef struct {
+  int images, h, w, classes; /* images = product of all leading dims; 1 <= classes <= 16; h, w <= 16384 */
+  int target_elem;           /* 0 uint8, 2 int64 */
+  int pred_elem;             /* 0 uint8, 2 int64 */
+  int has_ignore;
+  int64_t ignore_index;
+} OctContourDesc;
+size_t oct_contour_workspace_bytes(const OctContourDesc* d);
+int oct_contour_update(const OctContourDesc* d, const void* target, const void* pred, int64_t* records, void* workspace,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,12 @@ class SegEvalDesc(C.Structure):      # struct OctSegEvalDesc
                [("ignore_index", C.c_int64)]
 
 
+class ContourDesc(C.Structure):      # struct OctContourDesc
+    _fields_ = [(k, c_int) for k in ("images", "h", "w", "classes", "target_elem", "pred_elem", "has_ignore")] + \
+               [("ignore_index", C.c_int64)]
+
+
+CONTOUR_MAX_DIM = 16384   # h, w of oct_contour_update: keeps every squared distance below 2^31
 EVAL_PRED_U8, EVAL_PRED_I64, EVAL_PRED_NHWC_BF16, EVAL_PRED_NHWC_F32, EVAL_PRED_NCHW_F32 = range(5)   # OCT_EVAL_PRED_*
 EVAL_STATE_EXTRA = 4   # columns, ignored, invalid, updates behind cm [C*C] and thick_abs [C]
 
@@ -208,6 +214,8 @@ SIGNATURES = {
     "oct_sqdiff_sum": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_void_p]),
     "oct_column_absdiff_sum": (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_void_p]),
     "oct_seg_eval_update": (c_int, [C.POINTER(SegEvalDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_contour_workspace_bytes": (c_size_t, [C.POINTER(ContourDesc)]),
+    "oct_contour_update": (c_int, [C.POINTER(ContourDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

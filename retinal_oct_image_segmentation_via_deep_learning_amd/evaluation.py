@@ -22,6 +22,28 @@ which every update() ADDS to with one kernel launch and no host synchronisation;
 
 `metrics_from_state` is pure numpy: the formulas are Metrics._formulas (the reference's epsilons, verbatim) on the one-vs-rest
 counts that follow from the confusion matrix.
+
+Contour metrics (csrc/contour.hip, oct_contour_update): `BoundaryEvaluator` keeps, per image, class and direction, five exact
+int64 values on the device -- Hausdorff, HD95 and ASSD follow from them in `contour_metrics_from_records` (numpy, float64).
+
+  contour points of a mask M   the midpoints of the in-image pairs of 4-adjacent pixels with exactly one pixel in M: the vertex
+                               set of marching squares at level 0.5 (skimage.find_contours(M, 0.5)).  None along the image
+                               border: a full or an empty mask has no contour.  In doubled coordinates (2y, 2x+1) / (2y+1, 2x)
+                               the points are integral; D2 = squared distance there, true distance sqrt(D2) / 2 pixels.
+  classes                      M_c = {label == c}; a pixel whose target equals ignore_index is outside the image in both maps;
+                               labels outside [0, C) belong to no class.
+  record [image, c, dir]       n, max_d2, lo_d2, hi_d2, sum_q.  dir 0: from the points of pred to the nearest point of target
+                               (the reference's d1), dir 1 the reverse.  lo = 19 (n - 1) // 20, hi = min(lo + 1, n - 1) are the
+                               ranks np.percentile(., 95) interpolates between; sum_q = sum floor(2^16 sqrt(D2)).
+  f(v) = sqrt(v) / 2           HD = max_dir f(max_d2);  HD95 = max_dir f(lo) + frac (f(hi) - f(lo)), frac = (19 (n-1) % 20) / 20;
+                               ASSD = (sum_q[0] / n[0] + sum_q[1] / n[1]) / 2 / 2^17 (truncation <= 2^-17 px).  NaN unless
+                               both sides have a point.
+
+Deviations from the reference's Metrics/Contour_based_metrics.py, by decision: it scores only the FIRST contour find_contours
+returns (order-dependent) and counts the first vertex of a closed contour twice; here every contour counts and every vertex
+once.  For one simply connected object off the border hausdorff_distance is the same value, HD95 and ASSD differ by the weight
+of the repeated vertex.  Where the reference raises IndexError (a mask without a contour) the result is NaN.  skimage is not a
+dependency, so parity with the reference is by construction and not pinned by a test.
 """
 from __future__ import annotations
 
@@ -227,3 +249,150 @@ class SegEvaluator:
         if self.state is None:
             return metrics_from_state(np.zeros(state_size(self.classes), dtype=np.int64), self.classes)
         return metrics_from_state(self.state.cpu().numpy(), self.classes)
+
+
+# ---- contour metrics ------------------------------------------------------------------------------------------------------
+RECORD_FIELDS = ("n", "max_d2", "lo_d2", "hi_d2", "sum_q")
+
+
+def contour_metrics_from_records(records) -> dict:
+    """Hausdorff, HD95 and ASSD from the int64 records [images, C, 2, 5] (numpy float64, no GPU): see
+    BoundaryEvaluator.compute and the formulas in the module doc-string."""
+    r = np.asarray(records)
+    if r.dtype.kind not in "iu" or r.ndim != 4 or r.shape[2:] != (2, len(RECORD_FIELDS)):
+        raise ValueError(f"records must be integers of shape [images, C, 2, 5], got {r.dtype} {r.shape}")
+    r = r.astype(np.int64)
+    n, max_d2, lo_d2, hi_d2, sum_q = (r[..., k] for k in range(5))          # each [images, C, 2]
+    defined = (n > 0).all(axis=2)
+
+    def f(v):
+        return np.sqrt(v.astype(np.float64)) / 2.0
+
+    frac = ((19 * (n - 1)) % 20).astype(np.float64) / 20.0
+    flo = f(lo_d2)
+    p95 = flo + frac * (f(hi_d2) - flo)
+    mean_q = sum_q.astype(np.float64) / np.where(n > 0, n, 1)
+    nan = np.float64("nan")
+    res = {
+        "hausdorff": np.where(defined, f(max_d2).max(axis=2), nan),
+        "hd95": np.where(defined, p95.max(axis=2), nan),
+        "assd": np.where(defined, (mean_q[..., 0] + mean_q[..., 1]) / 2.0 / 2.0 ** 17, nan),
+        "defined": defined,
+        "images": int(r.shape[0]),
+    }
+    count = defined.sum(axis=0)
+    for k in ("hausdorff", "hd95", "assd"):
+        total = np.where(defined, res[k], 0.0).sum(axis=0)
+        res["mean_" + k] = np.where(count > 0, total / np.where(count > 0, count, 1), nan)
+    return res
+
+
+class BoundaryEvaluator:
+    """Hausdorff / HD95 / ASSD per image and class of a validation set; the records stay on the device until compute()."""
+
+    def __init__(self, classes, ignore_index=None, device=None, max_workspace_bytes=256 << 20):
+        _check_config(classes, ignore_index)
+        if isinstance(max_workspace_bytes, bool) or not isinstance(max_workspace_bytes, int) or max_workspace_bytes < 1:
+            raise ValueError(f"max_workspace_bytes must be a positive int, got {max_workspace_bytes!r}")
+        self.classes = classes
+        self.ignore_index = ignore_index
+        self.max_workspace_bytes = max_workspace_bytes
+        self.device = torch.device(device) if device is not None else None
+        if self.device is not None and self.device.type != "cuda":
+            raise L.OctError("BoundaryEvaluator needs a GPU device: there is no CPU fallback on the product path")
+        self._chunks = []        # int64 [images_i, C, 2, 5] device tensors, in update order
+        self._workspace = None   # uint8 device buffer, grown on demand, reused by every update
+
+    def _desc(self, images, h, w, target, pred):
+        return L.ContourDesc(images, h, w, self.classes, 0 if target.dtype == torch.uint8 else 2,
+                             0 if pred.dtype == torch.uint8 else 2, int(self.ignore_index is not None),
+                             int(self.ignore_index or 0))
+
+    def _check_device(self, device):
+        if device.type != "cuda":
+            raise L.OctError("the HIP path needs a device tensor (there is no CPU fallback)")
+        if self.device is not None and self.device.index is not None and device != self.device:
+            raise RuntimeError(f"inputs are on {device}, the evaluator was made for {self.device}")
+        if self._chunks and self._chunks[0].device != device:
+            raise RuntimeError(f"inputs are on {device}, the evaluator's records on {self._chunks[0].device}")
+
+    def reset(self):
+        self._chunks = []
+        return self
+
+    def update(self, target, pred):
+        """Two integer class maps of one shape (..., H, W), H, W <= 16384, with SegEvaluator.update's input rules.  The batch
+        goes through the kernel in chunks of images whose workspace fits max_workspace_bytes; one image that does not fit
+        raises.  Nothing is read back."""
+        target, pred = _class_map(target, "target"), _class_map(pred, "pred")
+        if target.shape != pred.shape:
+            raise RuntimeError(f"target {tuple(target.shape)} and pred {tuple(pred.shape)} must have the same shape")
+        if target.device != pred.device:
+            raise RuntimeError(f"target is on {target.device}, pred on {pred.device}")
+        h, w = target.shape[-2:]
+        if h < 1 or w < 1:
+            raise RuntimeError(f"class maps need H, W >= 1, got {tuple(target.shape)}")
+        if h > L.CONTOUR_MAX_DIM or w > L.CONTOUR_MAX_DIM:
+            raise RuntimeError(f"contour metrics take H, W <= {L.CONTOUR_MAX_DIM}, got {h} x {w}")
+        self._check_device(target.device)
+        images = target.numel() // (h * w)
+        if images == 0:
+            return self
+        lib = L.lib()
+        one = int(lib.oct_contour_workspace_bytes(C.byref(self._desc(1, h, w, target, pred))))
+        if one == 0:
+            raise L.OctError(f"oct_contour_workspace_bytes failed: {L.last_error()}")
+        if one > self.max_workspace_bytes:
+            raise RuntimeError(f"one {h} x {w} image with {self.classes} classes needs a workspace of {one} bytes, "
+                               f"max_workspace_bytes is {self.max_workspace_bytes}")
+        per = min(images, self.max_workspace_bytes // one, max(1, (2 ** 31 - 1) // (h * w)))   # bytes(k) <= k * bytes(1)
+        target, pred = target.reshape(images, h, w), pred.reshape(images, h, w)
+        out = torch.empty((images, self.classes, 2, len(RECORD_FIELDS)), dtype=torch.int64, device=target.device)
+        stream = torch.cuda.current_stream(target.device).cuda_stream
+        for lo in range(0, images, per):
+            k = min(per, images - lo)
+            desc = self._desc(k, h, w, target, pred)
+            need = int(lib.oct_contour_workspace_bytes(C.byref(desc)))
+            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != target.device:
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=target.device)
+            L.check(lib.oct_contour_update(C.byref(desc), target[lo:lo + k].data_ptr(), pred[lo:lo + k].data_ptr(),
+                                           out[lo:lo + k].data_ptr(), self._workspace.data_ptr(), stream), "oct_contour_update")
+        self._chunks.append(out)
+        return self
+
+    @torch.no_grad()
+    def update_model(self, model, x, target):
+        """model.predict(x) of an engine network (UNet, BioUNet, UNet3D) against target; the logits networks have no class
+        map of their own: pass theirs to update(target, class_map)."""
+        from .unet import _EngineNet
+        if not isinstance(model, _EngineNet):
+            raise TypeError(f"update_model takes an engine network with predict(); for {type(model).__name__} call "
+                            "update(target, class_map) with its arg-max")
+        if model._engine.ncls != self.classes:
+            raise RuntimeError(f"{type(model).__name__} has {model._engine.ncls} classes, the evaluator {self.classes}")
+        return self.update(target, model.predict(x))
+
+    def merge(self, records):
+        """Append records gathered elsewhere (another rank's records(), as a tensor or an array [images, C, 2, 5])."""
+        if not torch.is_tensor(records):
+            records = torch.from_numpy(np.ascontiguousarray(np.asarray(records)))
+        if records.dtype != torch.int64 or records.dim() != 4 or tuple(records.shape[1:]) != (self.classes, 2, len(RECORD_FIELDS)):
+            raise ValueError(f"records must be int64 [images, {self.classes}, 2, 5], got {records.dtype} {tuple(records.shape)}")
+        if self._chunks:
+            records = records.to(self._chunks[0].device)
+        self._chunks.append(records)
+        return self
+
+    def records(self):
+        """int64 [images, C, 2, 5] on the device, in update order (an empty CPU tensor before the first update)."""
+        if not self._chunks:
+            return torch.zeros((0, self.classes, 2, len(RECORD_FIELDS)), dtype=torch.int64)
+        if len(self._chunks) > 1:
+            self._chunks = [torch.cat(self._chunks, dim=0)]
+        return self._chunks[0]
+
+    def compute(self) -> dict:
+        """The only call that synchronises: per-image float64 arrays hausdorff, hd95, assd [images, C] in pixels (NaN where
+        a side has no contour), defined [images, C] bool, mean_hausdorff / mean_hd95 / mean_assd [C] over the defined images
+        (NaN without one), images."""
+        return contour_metrics_from_records(self.records().cpu().numpy())
