@@ -10,6 +10,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // thread-local error string (host side)
 void oct_set_error(const char* fmt, ...);
@@ -23,6 +25,8 @@ void oct_set_error(const char* fmt, ...);
 int oct_check_launch(const char* what);
 // more than 64 KB of dynamic LDS: opt the kernel in, once per (device, kernel); OCT_OK, or OCT_E_LAUNCH with the error set
 int oct_lds_optin(const void* kernel, int bytes);
+// the LDS of a gfx950 CU: the most a workgroup can be given.  Every kernel's LDS layout is checked against it.
+constexpr int OCT_LDS_CAP = 160 * 1024;
 
 // ---- convolution dispatch ----------------------------------------------------------------------------------------------
 // conv_dispatch.hip plans each descriptor once -- the kernel instantiation and its grid -- and the launch and the size queries
@@ -77,6 +81,16 @@ __device__ __forceinline__ float to_f32(bf16_t v) { return (float)v; }
 template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }
+// two floats rounded to bf16 in one dword (a in the low half), and the halves of such a dword back as floats
+__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  bf16x2 v;
+  v[0] = (bf16_t)a;
+  v[1] = (bf16_t)b;
+  return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ float bf16lo(unsigned u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bf16hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
 // V contiguous elements of T with natural vector alignment
 template <typename T, int V> struct alignas((sizeof(T) * V) > 16 ? 16 : (sizeof(T) * V)) VecT { T v[V]; };

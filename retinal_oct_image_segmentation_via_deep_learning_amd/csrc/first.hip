@@ -7,16 +7,6 @@
 // bf16 only; other dtypes / channel counts use the generic implicit-GEMM kernels.
 #include "common.h"
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned f1_pack(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = (bf16_t)a;
-  v[1] = (bf16_t)b;
-  return __builtin_bit_cast(unsigned, v);
-}
-
 // Position of a pixel as counters (x, y, slice): a thread walks pixels pix, pix + stride, ... and advances the counters by the
 // decomposition of `stride` instead of dividing -- q % w, (q / w) % h (and (q / plane) % depth three times per voxel in
 // the 3-D kernels) were ~45 of the ~220 vector instructions per pixel of these VALU-bound kernels.
@@ -112,7 +102,7 @@ __global__ void __launch_bounds__(256) first_fprop3d_kernel(const bf16_t* __rest
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] = fmaf(wv[kd * 9 + t][j], v[t], acc[j]);
     }
-    const u32x4 o = {f1_pack(acc[0], acc[1]), f1_pack(acc[2], acc[3]), f1_pack(acc[4], acc[5]), f1_pack(acc[6], acc[7])};
+    const u32x4 o = {pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3]), pack_bf16x2(acc[4], acc[5]), pack_bf16x2(acc[6], acc[7])};
     *reinterpret_cast<u32x4*>(y + (size_t)pix * F + g * 8) = o;
     if (stats) {
 #pragma unroll
@@ -182,7 +172,7 @@ __global__ void __launch_bounds__(256) first_fprop_kernel(const bf16_t* __restri
     for (int t = 0; t < 9; ++t)
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] = fmaf(wv[t][j], v[t], acc[j]);
-    const u32x4 o = {f1_pack(acc[0], acc[1]), f1_pack(acc[2], acc[3]), f1_pack(acc[4], acc[5]), f1_pack(acc[6], acc[7])};
+    const u32x4 o = {pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3]), pack_bf16x2(acc[4], acc[5]), pack_bf16x2(acc[6], acc[7])};
     *reinterpret_cast<u32x4*>(y + (size_t)pix * F + g * 8) = o;
     if (stats) {
 #pragma unroll
@@ -304,10 +294,9 @@ __global__ void __launch_bounds__(256) first_fprop_mfma_kernel(const bf16_t* __r
 #pragma unroll
       for (int ks = 1; ks < KS; ++ks) M::mma(acc, afr[cb][ks], bfr[ks]);
       // D[row = channel][col = pixel]: lane = pixel r, registers = channels (i&3) + 8*(i>>2) + 4*hh of the block
-      typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
-        const u32x2 pk = {f1_pack(acc[4 * gq], acc[4 * gq + 1]), f1_pack(acc[4 * gq + 2], acc[4 * gq + 3])};
+        const u32x2 pk = {pack_bf16x2(acc[4 * gq], acc[4 * gq + 1]), pack_bf16x2(acc[4 * gq + 2], acc[4 * gq + 3])};
         *reinterpret_cast<u32x2*>(sc + r * 80 + (8 * gq + 4 * hh) * 2) = pk;
       }
       if (stats) {
@@ -438,15 +427,6 @@ __global__ void __launch_bounds__(256) first_wgrad_kernel(const bf16_t* __restri
 // transposed (ds_read_b64_tr_b16, as wgrad2) and multiplies by the tap matrix -- lane T gathers the 8 consecutive input
 // pixels of its tap per k16 step (lanes T >= 9 and rows outside the image contribute zeros).  Replaces 72 FMAs and nine
 // bounds-checked loads per pixel and 8-channel group.
-typedef short f1_s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bf16x8 f1_tr_frag(const unsigned char* base_lo) {
-  typedef __attribute__((address_space(3))) f1_s16x4 lds_s16x4;
-  const f1_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo));
-  const f1_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo + 4 * 64));  // pixels +4
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 // KD = 3: Conv3d(1 -> F, 3x3x3) -- all 27 taps T = kd*9 + kh*3 + kw in ONE launch (dwp[T][co] = the [3][9][cout] slab of the
 // three per-depth-tap launches of the stencil kernel, which read dY three times)
@@ -542,7 +522,7 @@ __global__ void __launch_bounds__(256) first_wgrad_mfma_kernel(const bf16_t* __r
             const float gm = fmaf(yv[u], sc[j], sh[j]) > 0.f ? dv[u] : 0.f;
             o[u] = fmaf(k0[j], gm, fmaf(k1[j], yv[u], k2[j]));   // rounded to bf16 by the pack: what the unfused pass stores
           }
-          d[e] = f1_pack(o[0], o[1]);
+          d[e] = pack_bf16x2(o[0], o[1]);
         }
       }
       const unsigned c = lane + 64 * k;
@@ -565,7 +545,7 @@ __global__ void __launch_bounds__(256) first_wgrad_mfma_kernel(const bf16_t* __r
     for (int cb = 0; cb < NB; ++cb)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 afr = f1_tr_frag(&tile[wave][cb][0] + tr_off + ks * 16 * 64);
+        const bf16x8 afr = tr_frag(&tile[wave][cb][0] + tr_off + ks * 16 * 64);
         M::mma(acc[cb], afr, bfr[ks]);
       }
     asm volatile("" ::: "memory");

@@ -26,20 +26,19 @@ struct Gemm1Params {
   int n, h, w, c0, cout, ktot, nch, nk16, nblk, tiles_x, tiles_y, nitems, per_wg;
 };
 
-typedef unsigned int g1_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int g1_u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned g1_pack(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = (bf16_t)a;
-  v[1] = (bf16_t)b;
-  return __builtin_bit_cast(unsigned, v);
-}
-
 constexpr int G1_PIXB = 144;                // 64 bf16 + 16 B pad: conflict-free ds_read_b128 for the 32x32x16 lane map (9 r mod 16)
 constexpr int G1_BUFB = 256 * G1_PIXB;      // one 256-pixel x 64-channel chunk
 constexpr int G1_NBUF = 3;
+// The dynamic LDS of gemm1_kernel (byte offsets, each region starting where the one before it ends), for kernel and launcher
+struct G1Lds {
+  static constexpr int BUF = 0;                           // [G1_NBUF][G1_BUFB] chunk buffers
+  static constexpr int SXF = BUF + G1_NBUF * G1_BUFB;     // float [2][c0 <= 1024] scale | shift (XF)
+  static constexpr int OSCR = SXF + 2 * 1024 * 4;         // [8 waves][32 px][80 B] epilogue scratch
+  static constexpr int SBIAS = OSCR + 8 * 32 * 80;        // float [cout/4 <= 1024] (D2S)
+  static constexpr int BYTES = SBIAS + 1024 * 4;
+  static_assert((SXF | OSCR | SBIAS | BYTES) % 16 == 0, "every region stays 16-B aligned");
+  static_assert(BYTES <= OCT_LDS_CAP, "LDS budget");
+};
 
 // XF: BN + ReLU on load (forward); S2D: space-to-depth gather of the 2H x 2W input (data gradient); D2S: depth-to-space store
 template <bool XF, bool S2D, bool D2S>
@@ -47,10 +46,10 @@ __global__ void __launch_bounds__(512) gemm1_kernel(const Gemm1Params p) {
   typedef Mma<bf16_t> M;
   typedef M::Frag Frag;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* const buf0 = smem;
-  float* const sxf = reinterpret_cast<float*>(smem + G1_NBUF * G1_BUFB);            // [2][c0] scale | shift (XF)
-  unsigned char* const oscr = smem + G1_NBUF * G1_BUFB + 2 * 1024 * 4;                 // 8 waves x 32 px x 80 B
-  float* const sbias = reinterpret_cast<float*>(oscr + 8 * 32 * 80);                   // [cout/4] (D2S)
+  unsigned char* const buf0 = smem + G1Lds::BUF;
+  float* const sxf = reinterpret_cast<float*>(smem + G1Lds::SXF);       // [2][c0] scale | shift (XF)
+  unsigned char* const oscr = smem + G1Lds::OSCR;                       // 8 waves x 32 px x 80 B
+  float* const sbias = reinterpret_cast<float*>(smem + G1Lds::SBIAS);   // [cout/4] (D2S)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -124,13 +123,13 @@ __global__ void __launch_bounds__(512) gemm1_kernel(const Gemm1Params p) {
     return reinterpret_cast<const unsigned char*>(p.wp + ((size_t)nb * p.nk16 + t.pch * 4) * 512);   // uniform; the lane adds lane * 16
   };
   const unsigned wl = (unsigned)lane * 16u;
-  g1_u32x4 R[2][4];
+  u32x4 R[2][4];
   Frag W[4][2];          // [k16][q] of the chunk being multiplied; slot k16 is refilled for the next chunk right after its last use
   const size_t qs = (size_t)p.nk16 * 1024;
-  auto issue_x = [&](g1_u32x4 (&Rr)[4]) {
+  auto issue_x = [&](u32x4 (&Rr)[4]) {
     const unsigned char* const b = stage_base();
 #pragma unroll
-    for (int k = 0; k < 4; ++k) Rr[k] = *reinterpret_cast<const g1_u32x4*>(b + (size_t)goff[k]);
+    for (int k = 0; k < 4; ++k) Rr[k] = *reinterpret_cast<const u32x4*>(b + (size_t)goff[k]);
   };
   auto issue_w1 = [&](const unsigned char* b, int k16) {
 #pragma unroll
@@ -140,10 +139,10 @@ __global__ void __launch_bounds__(512) gemm1_kernel(const Gemm1Params p) {
     if (i_left > 0) { --i_left; it_next(it); }
   };
   int c_ch = rot;        // physical chunk of the stage being COMMITTED (for the BN coefficients); every item has nch stages
-  auto commit = [&](unsigned char* buf, const g1_u32x4 (&Rr)[4]) {
+  auto commit = [&](unsigned char* buf, const u32x4 (&Rr)[4]) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      g1_u32x4 v = Rr[k];
+      u32x4 v = Rr[k];
       if (XF) {
         const int cg = c_ch * 64 + (tid & 7) * 8;
         const f32x4 s0 = *reinterpret_cast<const f32x4*>(sxf + cg), s1 = *reinterpret_cast<const f32x4*>(sxf + cg + 4);
@@ -154,10 +153,10 @@ __global__ void __launch_bounds__(512) gemm1_kernel(const Gemm1Params p) {
         for (int j = 0; j < 4; ++j) {
           const float lo = fmaxf(fmaf(__uint_as_float(v[j] << 16), s[2 * j], bb[2 * j]), 0.f);
           const float hi = fmaxf(fmaf(__uint_as_float(v[j] & 0xffff0000u), s[2 * j + 1], bb[2 * j + 1]), 0.f);
-          v[j] = g1_pack(lo, hi);
+          v[j] = pack_bf16x2(lo, hi);
         }
       }
-      *reinterpret_cast<g1_u32x4*>(buf + ((tid + 512 * k) >> 3) * G1_PIXB + (tid & 7) * 16) = v;
+      *reinterpret_cast<u32x4*>(buf + ((tid + 512 * k) >> 3) * G1_PIXB + (tid & 7) * 16) = v;
     }
     if (++c_ch == p.nch) c_ch = 0;
   };
@@ -226,19 +225,19 @@ __global__ void __launch_bounds__(512) gemm1_kernel(const Gemm1Params p) {
             const f32x4 b4 = *reinterpret_cast<const f32x4*>(sbias + co + 8 * g + 4 * hh);
             a0 += b4[0]; a1 += b4[1]; a2 += b4[2]; a3 += b4[3];
           }
-          const g1_u32x2 v = {g1_pack(a0, a1), g1_pack(a2, a3)};
-          *reinterpret_cast<g1_u32x2*>(sc + r * 80 + (8 * g + 4 * hh) * 2) = v;
+          const u32x2 v = {pack_bf16x2(a0, a1), pack_bf16x2(a2, a3)};
+          *reinterpret_cast<u32x2*>(sc + r * 80 + (8 * g + 4 * hh) * 2) = v;
         }
-        g1_u32x4 tv[2];
+        u32x4 tv[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int chunk = lane + 64 * k;
-          tv[k] = *reinterpret_cast<const g1_u32x4*>(sc + (chunk >> 2) * 80 + (chunk & 3) * 16);
+          tv[k] = *reinterpret_cast<const u32x4*>(sc + (chunk >> 2) * 80 + (chunk & 3) * 16);
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int chunk = lane + 64 * k;
-          *reinterpret_cast<g1_u32x4*>(fb + (__umul24((unsigned)(chunk >> 2), pstep) + (unsigned)(chunk & 3) * 16u)) = tv[k];
+          *reinterpret_cast<u32x4*>(fb + (__umul24((unsigned)(chunk >> 2), pstep) + (unsigned)(chunk & 3) * 16u)) = tv[k];
         }
       }
     }
@@ -308,7 +307,7 @@ int launch_gemm1(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a,
   p.y = (bf16_t*)a->y0; p.bias = a->bias;
   p.n = d->n; p.h = d->h; p.w = d->w; p.c0 = d->c0; p.cout = d->cout; p.ktot = ktot; p.nch = ktot / 64; p.nk16 = ktot / 16;
   p.nblk = pl.nblk; p.tiles_x = d->w / 32; p.tiles_y = d->h / 8; p.nitems = pl.nitems; p.per_wg = pl.per_wg;
-  const int lds = G1_NBUF * G1_BUFB + 2 * 1024 * 4 + 8 * 32 * 80 + 1024 * 4;
+  constexpr int lds = G1Lds::BYTES;
   const auto kern = !fwd ? gemm1_kernel<false, true, false> : d->xform0 != OCT_XF_NONE ? gemm1_kernel<true, false, true> : gemm1_kernel<false, false, true>;
   if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), lds)) return rc;
   hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), lds, s, p);

@@ -31,28 +31,6 @@ struct HeadMfmaParams {
   float w_ce; int classes; unsigned npix;
 };
 
-typedef unsigned int hm_u32x4 __attribute__((ext_vector_type(4)));
-typedef short hm_s16x4 __attribute__((ext_vector_type(4)));
-
-// MFMA operand fragment with k = 8 consecutive pixels per lane from a [pixel][64 B] LDS block (see wgrad2.hip)
-__device__ __forceinline__ bf16x8 hm_tr_frag(const unsigned char* base_lo) {
-  typedef __attribute__((address_space(3))) hm_s16x4 lds_s16x4;
-  const hm_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo));
-  const hm_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo + 4 * 64));  // pixels +4
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ unsigned hm_pack(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = (bf16_t)a;
-  v[1] = (bf16_t)b;
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float hm_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float hm_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 __device__ __forceinline__ float hm_other(float v) { return __shfl_xor(v, 32); }            // lane r <-> lane r + 32
 __device__ __forceinline__ unsigned hm_other(unsigned v) { return (unsigned)__shfl_xor((int)v, 32); }
 
@@ -120,24 +98,24 @@ __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const Head
   const unsigned ngroups = (p.npix + 31) / 32;
   const unsigned gstride = gridDim.x * (HM_THREADS / 64);
   unsigned grp = blockIdx.x * (HM_THREADS / 64) + wave;
-  hm_u32x4 yn0, yn1;
+  u32x4 yn0, yn1;
   int tn;
   {
     const unsigned px = grp < ngroups ? min(grp * 32 + r, p.npix - 1) : 0u;
-    yn0 = *reinterpret_cast<const hm_u32x4*>(p.y + (size_t)px * F + 8 * hh);
-    yn1 = *reinterpret_cast<const hm_u32x4*>(p.y + (size_t)px * F + 16 + 8 * hh);
+    yn0 = *reinterpret_cast<const u32x4*>(p.y + (size_t)px * F + 8 * hh);
+    yn1 = *reinterpret_cast<const u32x4*>(p.y + (size_t)px * F + 16 + 8 * hh);
     tn = (int)p.target[px];
   }
   for (; grp < ngroups; grp += gstride) {
     const unsigned pix = grp * 32 + r;
     const bool valid = pix < p.npix;
-    const hm_u32x4 y0 = yn0, y1 = yn1;
+    const u32x4 y0 = yn0, y1 = yn1;
     const int t = tn;
     {
       const unsigned g2 = grp + gstride < ngroups ? grp + gstride : grp;
       const unsigned px = min(g2 * 32 + r, p.npix - 1);
-      yn0 = *reinterpret_cast<const hm_u32x4*>(p.y + (size_t)px * F + 8 * hh);
-      yn1 = *reinterpret_cast<const hm_u32x4*>(p.y + (size_t)px * F + 16 + 8 * hh);
+      yn0 = *reinterpret_cast<const u32x4*>(p.y + (size_t)px * F + 8 * hh);
+      yn1 = *reinterpret_cast<const u32x4*>(p.y + (size_t)px * F + 16 + 8 * hh);
       tn = (int)p.target[px];
     }
     // activation a = relu(y * scale + shift) as bf16 B fragments; z > 0 <=> a > 0 except at exact zeros
@@ -145,8 +123,8 @@ __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const Head
     unsigned apk[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      yv[2 * j] = hm_lo(y0[j]); yv[2 * j + 1] = hm_hi(y0[j]);
-      yv[8 + 2 * j] = hm_lo(y1[j]); yv[8 + 2 * j + 1] = hm_hi(y1[j]);
+      yv[2 * j] = bf16lo(y0[j]); yv[2 * j + 1] = bf16hi(y0[j]);
+      yv[8 + 2 * j] = bf16lo(y1[j]); yv[8 + 2 * j + 1] = bf16hi(y1[j]);
     }
     unsigned zmask = 0;      // bit k: pre-activation of feature k is positive
 #pragma unroll
@@ -156,8 +134,8 @@ __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const Head
       av[k] = fmaxf(z, 0.f);
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) apk[j] = hm_pack(av[2 * j], av[2 * j + 1]);
-    const hm_u32x4 a0 = {apk[0], apk[1], apk[2], apk[3]}, a1 = {apk[4], apk[5], apk[6], apk[7]};
+    for (int j = 0; j < 8; ++j) apk[j] = pack_bf16x2(av[2 * j], av[2 * j + 1]);
+    const u32x4 a0 = {apk[0], apk[1], apk[2], apk[3]}, a1 = {apk[4], apk[5], apk[6], apk[7]};
     const Frag xa0 = __builtin_bit_cast(Frag, a0), xa1 = __builtin_bit_cast(Frag, a1);
 
     // logits
@@ -208,10 +186,10 @@ __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const Head
       dl[i] = (valid && (4 * hh + i) < ncls) ? (float)(bf16_t)dl[i] : 0.f;   // as the unfused path would store it
       sdb[i] += dl[i];
     }
-    dpk[0] = hm_pack(dl[0], dl[1]); dpk[1] = hm_pack(dl[2], dl[3]);
+    dpk[0] = pack_bf16x2(dl[0], dl[1]); dpk[1] = pack_bf16x2(dl[2], dl[3]);
     // dl as a B fragment (k = class): lanes hh = 0 carry classes 0..7 (their own four + the partner's), hh = 1 zeros
     const unsigned o0 = hm_other(dpk[0]), o1 = hm_other(dpk[1]);
-    const hm_u32x4 dfr = {hh ? 0u : dpk[0], hh ? 0u : dpk[1], hh ? 0u : o0, hh ? 0u : o1};
+    const u32x4 dfr = {hh ? 0u : dpk[0], hh ? 0u : dpk[1], hh ? 0u : o0, hh ? 0u : o1};
     const Frag xd = __builtin_bit_cast(Frag, dfr);
     f32x16 acd;
 #pragma unroll
@@ -224,8 +202,8 @@ __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const Head
     unsigned cpk[8];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      cpk[2 * g] = hm_pack(acd[4 * g], acd[4 * g + 1]);
-      cpk[2 * g + 1] = hm_pack(acd[4 * g + 2], acd[4 * g + 3]);
+      cpk[2 * g] = pack_bf16x2(acd[4 * g], acd[4 * g + 1]);
+      cpk[2 * g + 1] = pack_bf16x2(acd[4 * g + 2], acd[4 * g + 3]);
     }
     // each lane sends the two pairs its partner needs: hh = 0 sends g = 1, 3; hh = 1 sends g = 0, 2
     const unsigned sA0 = hh ? cpk[0] : cpk[2], sA1 = hh ? cpk[1] : cpk[3];
@@ -240,25 +218,25 @@ __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const Head
       dq[4] = rB0; dq[5] = rB1; dq[6] = cpk[6]; dq[7] = cpk[7];
     }
     if (valid) {
-      const hm_u32x4 o0v = {dq[0], dq[1], dq[2], dq[3]}, o1v = {dq[4], dq[5], dq[6], dq[7]};
-      *reinterpret_cast<hm_u32x4*>(p.da + (size_t)pix * F + 8 * hh) = o0v;
-      *reinterpret_cast<hm_u32x4*>(p.da + (size_t)pix * F + 16 + 8 * hh) = o1v;
+      const u32x4 o0v = {dq[0], dq[1], dq[2], dq[3]}, o1v = {dq[4], dq[5], dq[6], dq[7]};
+      *reinterpret_cast<u32x4*>(p.da + (size_t)pix * F + 8 * hh) = o0v;
+      *reinterpret_cast<u32x4*>(p.da + (size_t)pix * F + 16 + 8 * hh) = o1v;
     }
     // BatchNorm-backward partial sums of the masked gradient, dA as stored; sum g*y converted at the end
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      const float d = (k & 1) ? hm_hi(dq[k >> 1]) : hm_lo(dq[k >> 1]);
+      const float d = (k & 1) ? bf16hi(dq[k >> 1]) : bf16lo(dq[k >> 1]);
       const float gm = (valid && ((zmask >> k) & 1u)) ? d : 0.f;
       s1[k] += gm;
       s2[k] = fmaf(gm, yv[k], s2[k]);
     }
     // dW[c][f] += sum over these 32 pixels dl[c] * a[f], both as stored (bf16): tiles to LDS, transposed reads
-    *reinterpret_cast<hm_u32x4*>(a_tile + r * 64 + 16 * hh) = a0;
-    *reinterpret_cast<hm_u32x4*>(a_tile + r * 64 + 32 + 16 * hh) = a1;
-    if (hh == 0) *reinterpret_cast<hm_u32x4*>(d_tile + r * 64) = dfr;
+    *reinterpret_cast<u32x4*>(a_tile + r * 64 + 16 * hh) = a0;
+    *reinterpret_cast<u32x4*>(a_tile + r * 64 + 32 + 16 * hh) = a1;
+    if (hh == 0) *reinterpret_cast<u32x4*>(d_tile + r * 64) = dfr;
 #pragma unroll
     for (int k16 = 0; k16 < 2; ++k16)
-      M::mma(accw, hm_tr_frag(d_tile + k16 * 16 * 64 + tr_off), hm_tr_frag(a_tile + k16 * 16 * 64 + tr_off));
+      M::mma(accw, tr_frag(d_tile + k16 * 16 * 64 + tr_off), tr_frag(a_tile + k16 * 16 * 64 + tr_off));
   }
 
   // ---- fold the 32 pixel lanes of each half-wave, then the waves of the workgroup -------------------------

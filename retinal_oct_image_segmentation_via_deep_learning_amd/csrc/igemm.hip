@@ -160,23 +160,33 @@ __device__ __forceinline__ void store4(const IgemmParams& p, int img, int oy, in
 
 // KH x KW kernel, stride 1, "same" padding ((KH-1)/2, (KW-1)/2): 3x3 and 1x1 for the U-Nets, 7x3 for ReLayNet's
 // BasicBlock (ReLayNet_2017.py:155-160).  tap = ky*KW + kx in the packed weights.
+// The dynamic LDS of igemm_kernel (byte offsets, each region starting where the one before it ends), for kernel and launcher
+template <typename T, int KH, int KW, int WM, int WN, int MF, int NF, int KC>
+struct IgemmLds {
+  static constexpr int TH = WM * MF, TW = 32, LH = TH + KH - 1, LW = TW + KW - 1;
+  static constexpr int PIXB = KC * (int)sizeof(T) + 16;  // LDS bytes per pixel (+16: conflict-free b128 reads)
+  static constexpr int NT = WN * NF * 32;
+  static constexpr int TILE = 0;                          // [LH * LW pixels][PIXB] halo tile
+  static constexpr int WG_STATS = TILE + LH * LW * PIXB;  // float [WM][2][NT] statistics
+  static constexpr int BYTES = WG_STATS + WM * 2 * NT * (int)sizeof(float);
+  static_assert((WG_STATS | BYTES) % 16 == 0, "every region stays 16-B aligned");
+  static_assert(BYTES <= OCT_LDS_CAP, "LDS budget");
+};
+
 template <typename T, int KH, int KW, int WM, int WN, int MF, int NF, int KC>
 __global__ void __launch_bounds__(256) igemm_kernel(const IgemmParams p) {
   static_assert(WM * WN == 4, "four waves per workgroup");
+  typedef IgemmLds<T, KH, KW, WM, WN, MF, NF, KC> L;
   constexpr int TAPS = KH * KW;
-  constexpr int TH = WM * MF, TW = 32;
+  constexpr int TH = L::TH, TW = L::TW, LH = L::LH, LW = L::LW, PIXB = L::PIXB, NT = L::NT;
   constexpr int HALO_H = (KH - 1) / 2, HALO_W = (KW - 1) / 2;
-  constexpr int LH = TH + KH - 1, LW = TW + KW - 1;
-  constexpr int PIXB = KC * (int)sizeof(T) + 16;  // LDS bytes per pixel (+16: conflict-free b128 reads)
-  constexpr int NT = WN * NF * 32;
   constexpr int GROUPS = KC / 8;
   typedef Mma<T> M;
   typedef typename M::Frag Frag;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char ig_smem[];   // halo tile, then [WM][2][NT] statistics
-  unsigned char* const tile = ig_smem;
-  float (*const wg_stats)[2][NT] = reinterpret_cast<float (*)[2][NT]>(ig_smem + LH * LW * PIXB);
-  static_assert((LH * LW * PIXB) % 16 == 0, "statistics scratch stays aligned");
+  unsigned char* const tile = ig_smem + L::TILE;
+  float (*const wg_stats)[2][NT] = reinterpret_cast<float (*)[2][NT]>(ig_smem + L::WG_STATS);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
@@ -486,8 +496,7 @@ void igemm_plan(const OctConvDesc* d, ConvPlan* pl) {
 
 template <typename T, int KH, int KW, int WM, int WN, int MF, int NF>
 static int launch_igemm_cfg(const IgemmParams& p, dim3 grid, hipStream_t s) {
-  constexpr int TH = WM * MF, NT = WN * NF * 32, PIXB = 32 * (int)sizeof(T) + 16;
-  constexpr int lds = (TH + KH - 1) * (32 + KW - 1) * PIXB + WM * 2 * NT * (int)sizeof(float);
+  constexpr int lds = IgemmLds<T, KH, KW, WM, WN, MF, NF, 32>::BYTES;
   if (lds > 64 * 1024)   // 7x3 in fp32: 14 x 34 pixels x 144 B
     if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&igemm_kernel<T, KH, KW, WM, WN, MF, NF, 32>), lds)) return rc;
   hipLaunchKernelGGL((igemm_kernel<T, KH, KW, WM, WN, MF, NF, 32>), grid, dim3(256), lds, s, p);

@@ -36,8 +36,6 @@ struct Igemm2Params {
   unsigned long long* trace;  // diagnostic builds only (-DOCT_TRACE): s_memtime stamps of workgroup 0
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #ifdef OCT_TRACE
 #define TRACE(slot, idx)                                                                              \
   do {                                                                                                \
@@ -50,15 +48,6 @@ extern "C" void oct_debug_set_trace(void* buf) { g_trace = (unsigned long long*)
 #define TRACE(slot, idx) do {} while (0)
 #endif
 
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = (bf16_t)a;
-  v[1] = (bf16_t)b;
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float bf16lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
 // RAGGED: H or W is not a multiple of the tile; whole-tile shapes (the benchmark) run the instantiation
 // without any of the predication below (measured: 2-3 % when it was unconditional).
@@ -75,6 +64,43 @@ template <int TAPS, int NF, bool WRES> constexpr bool ig2_m16() { return TAPS !=
 //                                                          16x16x32 kernels on: every activation read paid a 2-way conflict)
 // DMA tiles are dense (64 B) with the swizzle on the source address.  tools/lds_swizzle_check.py enumerates all of these.
 template <int TAPS, int NF, bool WRES, bool DMA> constexpr int ig2_pixb() { return DMA ? 64 : (ig2_m16<TAPS, NF, WRES>() ? 96 : 80); }
+
+// The dynamic LDS of igemm2_kernel, by the template parameters that shape it (STATS, RAGGED and D3 do not).  Byte offsets;
+// every region starts where the one before it ends.  The kernel takes its pointers from here and the launcher its byte count.
+template <int TAPS, int WM, int WN, int MF, int NF, bool WRES, bool DMA, bool WLDS, bool FUSE>
+struct Ig2Lds {
+  static constexpr int TH = WM * MF, TW = 32;
+  // TAPS = 9: 3x3; TAPS = 21: 7x3 (ReLayNet_2017.py:155-160, padding (3, 1)): tap = ky * 3 + kx either way; TAPS = 1: 1x1
+  static constexpr int HALO = (TAPS != 1) ? 1 : 0;              // columns
+  static constexpr int HALO_Y = (TAPS == 21) ? 3 : HALO;        // rows
+  static constexpr int LH = TH + 2 * HALO_Y, LW = TW + 2 * HALO;
+  static constexpr int NPIX = LH * LW;
+  static constexpr int NSLOT = (NPIX + 63) / 64;       // producers (4 waves): 64 pixels x 4 channel groups per pass
+  static constexpr int PIXB = ig2_pixb<TAPS, NF, WRES, DMA>();
+  static constexpr int BUFB = DMA ? NSLOT * 4096 : NPIX * PIXB;
+  static constexpr int NBUF = DMA ? (TAPS != 1 ? 3 : 6) : 2;
+  static constexpr int NT = WN * NF * 32;
+  // WLDS trims the tables to what a 3x3 kernel with <= 64 input channels needs, to make room for the filter
+  static constexpr int SXF_N = WLDS ? 64 : 1024, OSCR_SLOTS = WLDS ? 1 : 2, SBIAS_N = WLDS ? 0 : 1024;
+  static constexpr int XTB = TH * TW * 64;             // FUSE: one interior tile of x, [TH * 32 pixels][64 B]
+
+  static constexpr int BUF = 0;                                      // [NBUF][BUFB] halo tiles
+  static constexpr int WG_STATS = BUF + NBUF * BUFB;                 // float [2 parity][WM][2][NT], 4 floats of pad
+  static constexpr int SXF = WG_STATS + (2 * WM * 2 * NT + 4) * 4;   // float [2][SXF_N] scale | shift of the input channels
+  static constexpr int OSCR = SXF + 2 * SXF_N * 4;                   // [OSCR_SLOTS][4 waves][32 px][80 B] epilogue scratch
+  static constexpr int OSCR_BYTES = OSCR_SLOTS * 4 * 32 * 80;
+  static constexpr int WFILT = OSCR + OSCR_BYTES;                    // [tap][k16][1 KB fragment] the filter (WLDS)
+  static constexpr int SBIAS = WFILT + (WLDS ? 2 * 18 * 1024 : 0);   // float [cout/4] deconv bias (D2S only)
+  static constexpr int TAIL = SBIAS + SBIAS_N * 4;                   // what follows depends on the launch:
+  static constexpr int WGACC = TAIL;                                 // float [2][cout] BatchNorm sums of the workgroup (run time)
+  static constexpr int FXT = TAIL, FXR = FXT + 2 * XTB;              // FUSE: [2 buffers][XTB] transformed x, then the same of raw x
+  static constexpr int FIXED = FUSE ? FXR + 2 * XTB : TAIL;
+  // stats_cout: cout of a launch that wants BatchNorm sums (resident weights: sums in registers, the tail stays untouched), else 0
+  static constexpr int bytes(int stats_cout) { return FIXED + 2 * stats_cout * 4; }
+  static constexpr int MAX_COUT = NT == 32 ? 32 : 4096;   // largest cout igemm2_plan sends here: a 32-channel tiling serves cout = 32 only
+  static_assert((WG_STATS | SXF | OSCR | WFILT | SBIAS | TAIL | FXR | FIXED) % 16 == 0, "every region stays 16-B aligned");
+  static_assert(FIXED <= OCT_LDS_CAP, "LDS budget");
+};
 
 // 16 zero bytes in device memory: the source of every LDS-DMA lane whose pixel is padding (a DMA cannot write a constant)
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4];
@@ -112,17 +138,9 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
                 "fused backward: resident weights, 32 -> 32 channels, whole tiles, 2-D");
   static_assert(!DMA || (!WRES && !STATS && !RAGGED && !D3), "DMA staging: streamed weights, whole tiles, 2-D, no BatchNorm sums");
   static_assert(!WLDS || (TAPS == 9 && !WRES && !D3 && !DMA && WN * NF == 1), "LDS-resident weights: 3x3, one 32-channel block");
-  constexpr int TH = WM * MF, TW = 32;
-  // TAPS = 9: 3x3; TAPS = 21: 7x3 (ReLayNet_2017.py:155-160, padding (3, 1)): tap = ky * 3 + kx either way; TAPS = 1: 1x1
-  constexpr int HALO = (TAPS != 1) ? 1 : 0;              // columns
-  constexpr int HALO_Y = (TAPS == 21) ? 3 : HALO;        // rows
-  constexpr int LH = TH + 2 * HALO_Y, LW = TW + 2 * HALO;
-  constexpr int NPIX = LH * LW;
-  constexpr int NSLOT = (NPIX + 63) / 64;       // producers (4 waves): 64 pixels x 4 channel groups per pass
-  constexpr int PIXB = ig2_pixb<TAPS, NF, WRES, DMA>();
-  constexpr int BUFB = DMA ? NSLOT * 4096 : NPIX * PIXB;
-  constexpr int NBUF = DMA ? (TAPS != 1 ? 3 : 6) : 2;
-  constexpr int NT = WN * NF * 32;
+  typedef Ig2Lds<TAPS, WM, WN, MF, NF, WRES, DMA, WLDS, FUSE> L;
+  constexpr int TH = L::TH, TW = L::TW, HALO = L::HALO, HALO_Y = L::HALO_Y, LH = L::LH, LW = L::LW, NPIX = L::NPIX, NSLOT = L::NSLOT;
+  constexpr int PIXB = L::PIXB, BUFB = L::BUFB, NBUF = L::NBUF, NT = L::NT, SXF_N = L::SXF_N, XTB = L::XTB;
   constexpr int KSTEPS = TAPS * 2;              // k16 steps per 32-channel chunk
   // M16: the streamed-weight 3x3 kernels multiply with v_mfma_f32_16x16x32_bf16 -- 18 half-steps (tap, 16-pixel half) of
   // MF * 2NF MFMAs per stage instead of 18 k16 steps of MF * NF.  Same FLOPs per cycle, same LDS and weight bytes, same
@@ -136,8 +154,24 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
   typedef M::Frag Frag;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* const buf0 = smem;
-  float* const wg_stats = reinterpret_cast<float*>(smem + NBUF * BUFB);  // [2 parity][WM][2][NT]
+  unsigned char* const buf0 = smem + L::BUF;
+  float* const wg_stats = reinterpret_cast<float*>(smem + L::WG_STATS);  // [2 parity][WM][2][NT]
+  // BN scale/shift of every input channel live in LDS: reading them with ds_read keeps them off the
+  // vmcnt queue (a global load issued at commit time would be YOUNGER than the prefetched stages and
+  // waiting for it would drain the whole ring -- vmcnt retires in order)
+  float* const sxf = reinterpret_cast<float*>(smem + L::SXF);
+  unsigned char* const oscr = smem + L::OSCR;                            // OSCR_SLOTS x 4 waves x 32 px x 80 B
+  unsigned char* const wlds = smem + L::WFILT;                           // [tap][k16][1 KB fragment] (WLDS)
+  float* const sbias = reinterpret_cast<float*>(smem + L::SBIAS);        // [cout/4] deconv bias (D2S only)
+  // streamed-weight kernels: BatchNorm partial sums of ALL items of this workgroup, [2][cout]; one row
+  // per workgroup reaches memory instead of one per tile (bn_finalize then reads <= 512 rows, not 16 k)
+  float* const wgacc = reinterpret_cast<float*>(smem + L::WGACC);
+  // FUSE: interior tiles of x, [2 buffers][TH * 32 pixels][64 B] each: transformed (dW operand), then raw (BatchNorm sums)
+  unsigned char* const fxt = smem + L::FXT;
+  unsigned char* const fxr = smem + L::FXR;
+  // the run-time tail (launches with STATS get it) at the largest cout of this tiling.  The 16-row 64-channel tiling has room
+  // for cout <= 1152 only: the launcher refuses a larger one
+  static_assert(!STATS || L::bytes(L::MAX_COUT) <= OCT_LDS_CAP || (TH == 16 && NT == 64), "LDS budget with the BatchNorm sums");
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // in an SGPR: everything derived from it stays scalar
@@ -164,23 +198,6 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
   const int nstage = nitems_wg * p.nch;
   const int nstage_pad = (nstage + 3) / 4 * 4;   // a multiple of the producer ring depth (D = 2; 4 keeps the unrolled bodies' parity)
 
-  // BN scale/shift of every input channel live in LDS: reading them with ds_read keeps them off the
-  // vmcnt queue (a global load issued at commit time would be YOUNGER than the prefetched stages and
-  // waiting for it would drain the whole ring -- vmcnt retires in order)
-  // WLDS trims the tables to what a 3x3 kernel with <= 64 input channels needs, to make room for the filter
-  constexpr int SXF_N = WLDS ? 64 : 1024, OSCR_SLOTS = WLDS ? 1 : 2, SBIAS_N = WLDS ? 0 : 1024, WLDS_BYTES = WLDS ? 2 * 18 * 1024 : 0;
-  float* const sxf = reinterpret_cast<float*>(smem + NBUF * BUFB) + (2 * WM * 2 * NT + 4);
-  unsigned char* const oscr = smem + NBUF * BUFB + (2 * WM * 2 * NT + 4) * 4 + 2 * SXF_N * 4;  // OSCR_SLOTS x 4 waves x 32 px x 80 B
-  static_assert((NBUF * BUFB + (2 * WM * 2 * NT + 4) * 4) % 16 == 0, "scratch must stay 16-B aligned");
-  unsigned char* const wlds = oscr + OSCR_SLOTS * 4 * 32 * 80;               // [tap][k16][1 KB fragment] (WLDS)
-  float* const sbias = reinterpret_cast<float*>(wlds + WLDS_BYTES);          // [cout/4] deconv bias (D2S only)
-  // streamed-weight kernels: BatchNorm partial sums of ALL items of this workgroup, [2][cout]; one row
-  // per workgroup reaches memory instead of one per tile (bn_finalize then reads <= 512 rows, not 16 k)
-  float* const wgacc = sbias + SBIAS_N;
-  // FUSE: interior tiles of x, [2 buffers][TH * 32 pixels][64 B] each: transformed (dW operand), then raw (BatchNorm sums)
-  constexpr int XTB = TH * TW * 64;
-  unsigned char* const fxt = reinterpret_cast<unsigned char*>(sbias + SBIAS_N);
-  unsigned char* const fxr = fxt + 2 * XTB;
   if (STATS && !WRES) {
     for (int i = tid; i < 2 * p.cout; i += 512) wgacc[i] = 0.f;
   }
@@ -721,7 +738,6 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
       e_pstep[q] = (d2s ? 4u : 2u) * (unsigned)cd;                  // bytes between horizontally adjacent output pixels
     }
   };
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
   // A fragment leaves in three moves: (1) bf16 pairs into the wave-private LDS scratch, pixel-major, so that
   // (2) consecutive lanes read back consecutive 16-B chunks (whole 64-B channel rows per pixel) and (3) store them.
   auto frag_to_lds = [&](const unsigned (&pk)[8], int slot = 0) {
@@ -932,6 +948,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
       // lane base; the row (m + ty) stays a compile-time offset
       constexpr int NTX = (TAPS != 1) ? 3 : 1;
       unsigned lbs[DMA ? NTX : 1][2];   // byte offsets from smem (32-bit: six 64-bit pointers cost the dgrad kernels their last registers)
+      static_assert(L::BUF == 0, "lbs / lbs16 index the tile buffers from smem itself");
       if constexpr (DMA && !M16) {
 #pragma unroll
         for (int tx = 0; tx < NTX; ++tx)
@@ -1135,7 +1152,7 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
         {
           constexpr int P2 = 144;        // scratch pitch: 128 B of channels + 16 B pad
           unsigned char* const sc2 = oscr + wave * (32 * P2);
-          static_assert(32 * P2 <= OSCR_SLOTS * 32 * 80, "the merged tile fits the wave's scratch");
+          static_assert(32 * P2 <= L::OSCR_BYTES / 4, "the merged tile fits the wave's scratch");
           u32x4 tv4[4];
           int pm2 = -1;
           auto store4 = [&](int mm) {
@@ -1357,6 +1374,21 @@ __global__ void __launch_bounds__(512) igemm2_kernel(const Igemm2Params p) {
 // kernel codes of ConvPlan on this path
 enum { IG2_TILE, IG2_1X1, IG2_WLDS, IG2_DMA };
 
+// The persistent walk over `ntiles` tiles of pl->nblk channel blocks each: items, grid and the rows of partial sums
+static void ig2_walk(int ntiles, ConvPlan* pl) {
+  pl->nitems = ntiles * pl->nblk;
+  int target = 256;  // one persistent workgroup per CU (only one fits the LDS); 512 measured 2 % slower on dgrad, 1024 4 %
+  if (target > pl->nitems) target = pl->nitems;
+  pl->per_wg = (pl->nitems + target - 1) / target;
+  pl->grid = (pl->nitems + pl->per_wg - 1) / pl->per_wg;
+  pl->interleave = 0;
+  if (ntiles >= 2 * target) {   // interleaved tile walk: one workgroup per CU, tiles b, b + 256, ...
+    pl->grid = target;
+    pl->interleave = 1;
+  }
+  pl->stat_rows = pl->grid;   // one row of sums per (persistent) workgroup: every workgroup of the grid has a tile
+}
+
 bool igemm2_plan(const OctConvDesc* d, ConvPlan* out) {
   if (d->kh == 7) {
     // 7x3 (ReLayNet): the 64- and 128-channel tilings with three halo rows above and below an 8-row tile.  A last tile row of
@@ -1396,17 +1428,7 @@ bool igemm2_plan(const OctConvDesc* d, ConvPlan* out) {
   // concat split inside them -- split % 64 != 0 -- keeps the one-fragment tiling.
   pl.th = (d->taps == 9 && (pl.nt == 32 || (pl.nt == 64 && !pl.wres && (d->split % 64) == 0)) && (d->h % 16) == 0) ? 16 : 8;
   const int ntiles = ((d->w + 31) / 32) * ((d->h + pl.th - 1) / pl.th) * d->n;
-  pl.nitems = ntiles * pl.nblk;
-  int target = 256;  // one persistent workgroup per CU (only one fits the LDS); 512 measured 2 % slower on dgrad, 1024 4 %
-  if (target > pl.nitems) target = pl.nitems;
-  pl.per_wg = (pl.nitems + target - 1) / target;
-  pl.grid = (pl.nitems + pl.per_wg - 1) / pl.per_wg;
-  pl.interleave = 0;
-  if (ntiles >= 2 * target) {   // interleaved tile walk: one workgroup per CU, tiles b, b + 256, ...
-    pl.grid = target;
-    pl.interleave = 1;
-  }
-  pl.stat_rows = pl.grid;   // one row [2][cout] per (persistent) workgroup
+  ig2_walk(ntiles, &pl);
   // LDS-DMA staging (see the kernel): data gradients -- one source, no transform on load, whole 8-row tiles, streamed weights
   // (7x3: the LDS-DMA variant spills 8 dwords and measured 1 % slower on ReLayNet's data gradients)
   const bool dma = !d->xform0 && !d->xform1 && d->c1 == 0 && !d->want_stats && !pl.wres && pl.th == 8 &&
@@ -1420,14 +1442,20 @@ bool igemm2_plan(const OctConvDesc* d, ConvPlan* out) {
   return true;
 }
 
-// > 64 KB of dynamic LDS: every variant opts in to the 160 KB cap
+// One launch of `kern` with the dynamic LDS of its layout L (> 64 KB: every variant opts in to the cap).  p.stats: the launch
+// wants BatchNorm sums and gets the [2][cout] tail.
+template <class L>
+static int ig2_launch(void (*kern)(Igemm2Params), const Igemm2Params& p, int grid, hipStream_t s) {
+  const int lds = L::bytes(p.stats ? p.cout : 0);
+  OCT_CHECK(lds <= OCT_LDS_CAP, "igemm2: %d bytes of LDS for cout = %d, the cap is %d", lds, p.cout, OCT_LDS_CAP);
+  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), OCT_LDS_CAP)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
+  return OCT_OK;
+}
 template <int WM, int WN, int MF, int NF, bool WRES, int TAPS = 9>
 static int launch_v2(const Igemm2Params& p, int grid, hipStream_t s) {
-  constexpr int TH = WM * MF;
-  constexpr int LH = TH + (TAPS == 21 ? 6 : 2);   // halo rows: 3 + 3 for the 7x3 kernel
-  const int lds = 2 * LH * 34 * ig2_pixb<TAPS, NF, WRES, false>() + (2 * WM * 2 * (WN * NF * 32) + 4 + 2 * 1024) * (int)sizeof(float) + 2 * 4 * 32 * 80 + 1024 * (int)sizeof(float) +
-                  (p.stats ? 2 * p.cout * (int)sizeof(float) : 0);
-  const bool ragged = (p.w % 32) != 0 || (p.h % TH) != 0;
+  typedef Ig2Lds<TAPS, WM, WN, MF, NF, WRES, false, false, false> L;
+  const bool ragged = (p.w % 32) != 0 || (p.h % L::TH) != 0;
   void (*kern)(Igemm2Params) = nullptr;
   if (p.depth > 0) {   // volumetric: whole tiles only (igemm2_plan), streamed weights
     if constexpr (!WRES && TAPS == 9)
@@ -1438,46 +1466,32 @@ static int launch_v2(const Igemm2Params& p, int grid, hipStream_t s) {
     kern = p.stats ? igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, true> : igemm2_kernel<TAPS, WM, WN, MF, NF, WRES, false>;
   }
   if (!kern) { oct_set_error("igemm2: no depth-tap instantiation of this tiling"); return OCT_E_INVALID; }
-  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
-  return OCT_OK;
+  return ig2_launch<L>(kern, p, grid, s);
 }
 template <int WM, int WN, int MF, int NF>
 static int launch_v2_1x1(const Igemm2Params& p, int grid, hipStream_t s) {
-  constexpr int TH = WM * MF;
-  const int lds = 2 * TH * 32 * 80 + (2 * WM * 2 * (WN * NF * 32) + 4 + 2 * 1024) * (int)sizeof(float) + 2 * 4 * 32 * 80 + 1024 * (int)sizeof(float) +
-                  (p.stats ? 2 * p.cout * (int)sizeof(float) : 0);
-  const bool ragged = (p.w % 32) != 0 || (p.h % TH) != 0;
+  typedef Ig2Lds<1, WM, WN, MF, NF, false, false, false, false> L;
+  const bool ragged = (p.w % 32) != 0 || (p.h % L::TH) != 0;
+  void (*kern)(Igemm2Params);
   if (p.in_mode == OCT_IN_PLAIN && p.out_mode == OCT_OUT_PLAIN && (p.stats || ragged)) {   // plain 1x1 convolution with BN sums / ragged tiles
-    if (ragged) {
-      if (p.stats) hipLaunchKernelGGL((igemm2_kernel<1, WM, WN, MF, NF, false, true, true>), dim3(grid), dim3(512), lds, s, p);
-      else hipLaunchKernelGGL((igemm2_kernel<1, WM, WN, MF, NF, false, false, true>), dim3(grid), dim3(512), lds, s, p);
-    } else hipLaunchKernelGGL((igemm2_kernel<1, WM, WN, MF, NF, false, true>), dim3(grid), dim3(512), lds, s, p);
+    if (ragged) kern = p.stats ? igemm2_kernel<1, WM, WN, MF, NF, false, true, true> : igemm2_kernel<1, WM, WN, MF, NF, false, false, true>;
+    else kern = igemm2_kernel<1, WM, WN, MF, NF, false, true>;
   } else if (p.depth > 0 || p.oimg_mul)
-    hipLaunchKernelGGL((igemm2_kernel<1, WM, WN, MF, NF, false, false, false, true>), dim3(grid), dim3(512), lds, s, p);
+    kern = igemm2_kernel<1, WM, WN, MF, NF, false, false, false, true>;
   else
-    hipLaunchKernelGGL((igemm2_kernel<1, WM, WN, MF, NF, false, false>), dim3(grid), dim3(512), lds, s, p);
-  return OCT_OK;
+    kern = igemm2_kernel<1, WM, WN, MF, NF, false, false>;
+  return ig2_launch<L>(kern, p, grid, s);
 }
 template <int WM, int MF>
 static int launch_v2_wlds(const Igemm2Params& p, int grid, hipStream_t s) {
-  constexpr int TH = WM * MF;
-  const int lds = 2 * (TH + 2) * 34 * 80 + (2 * WM * 2 * 32 + 4) * (int)sizeof(float) + 2 * 64 * (int)sizeof(float) + 4 * 32 * 80 + 2 * 18 * 1024 +
-                  (p.stats ? 2 * p.cout * (int)sizeof(float) : 0);
-  const auto kern = p.stats ? igemm2_kernel<9, WM, 1, MF, 1, false, true, false, false, false, true> : igemm2_kernel<9, WM, 1, MF, 1, false, false, false, false, false, true>;
-  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
-  return OCT_OK;
+  typedef Ig2Lds<9, WM, 1, MF, 1, false, false, true, false> L;
+  return ig2_launch<L>(p.stats ? igemm2_kernel<9, WM, 1, MF, 1, false, true, false, false, false, true>
+                               : igemm2_kernel<9, WM, 1, MF, 1, false, false, false, false, false, true>, p, grid, s);
 }
 template <int TAPS, int WM, int WN, int MF, int NF>
-static int launch_v2_dma(const Igemm2Params& p, int grid, hipStream_t s) {
-  constexpr int TH = WM * MF, HALO = TAPS != 1 ? 1 : 0, HALO_Y = TAPS == 21 ? 3 : HALO;
-  constexpr int NSLOT = ((TH + 2 * HALO_Y) * (32 + 2 * HALO) + 63) / 64, NBUF = TAPS != 1 ? 3 : 6;
-  constexpr int lds = NBUF * NSLOT * 4096 + (2 * WM * 2 * (WN * NF * 32) + 4 + 2 * 1024) * (int)sizeof(float) + 2 * 4 * 32 * 80 + 1024 * (int)sizeof(float);
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&igemm2_kernel<TAPS, WM, WN, MF, NF, false, false, false, false, true>), lds)) return rc;
-  hipLaunchKernelGGL((igemm2_kernel<TAPS, WM, WN, MF, NF, false, false, false, false, true>), dim3(grid), dim3(512), lds, s, p);
-  return OCT_OK;
+static int launch_v2_dma(const Igemm2Params& p, int grid, hipStream_t s) {   // no BatchNorm sums on this path (igemm2_plan)
+  typedef Ig2Lds<TAPS, WM, WN, MF, NF, false, true, false, false> L;
+  return ig2_launch<L>(igemm2_kernel<TAPS, WM, WN, MF, NF, false, false, false, false, true>, p, grid, s);
 }
 
 int launch_igemm2(const ConvPlan& pl, const OctConvDesc* d, const OctConvArgs* a, hipStream_t s) {
@@ -1539,14 +1553,7 @@ bool igemm2_fused_plan(const OctWgradDesc* d, ConvPlan* out) {
   pl.path = CONV_IGEMM2;
   pl.kernel = IG2_TILE;
   pl.nt = 32; pl.wres = true; pl.nblk = 1; pl.th = 8;
-  const int ntiles = (d->w / 32) * (d->h / 8) * d->n;
-  pl.nitems = ntiles;
-  const int target = ntiles < 256 ? ntiles : 256;   // one persistent workgroup per CU, as the data gradient alone
-  pl.per_wg = (ntiles + target - 1) / target;
-  pl.grid = (ntiles + pl.per_wg - 1) / pl.per_wg;
-  pl.interleave = 0;
-  if (ntiles >= 2 * target) { pl.grid = target; pl.interleave = 1; }
-  pl.stat_rows = pl.grid;   // one row [2][cin] of BatchNorm-backward sums per workgroup: every workgroup of the grid has a tile
+  ig2_walk((d->w / 32) * (d->h / 8) * d->n, &pl);   // as the data gradient alone; stat_rows: [2][cin] BatchNorm-backward sums each
   *out = pl;
   return true;
 }
@@ -1564,12 +1571,7 @@ int launch_igemm2_fused(const ConvPlan& pl, const OctWgradDesc* d, const OctConv
 #ifdef OCT_TRACE
   p.trace = g_trace;
 #endif
-  constexpr int TH = 8;
-  constexpr int lds = 2 * (TH + 2) * 34 * ig2_pixb<9, 1, true, false>() + (2 * 4 * 2 * 32 + 4 + 2 * 1024) * (int)sizeof(float) + 2 * 4 * 32 * 80 +
-                      1024 * (int)sizeof(float) + 4 * TH * 32 * 64;
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  const auto kern = igemm2_kernel<9, 4, 1, 2, 1, true, false, false, false, false, false, true>;
-  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
-  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), lds, s, p);
+  typedef Ig2Lds<9, 4, 1, 2, 1, true, false, false, true> L;
+  if (const int rc = ig2_launch<L>(igemm2_kernel<9, 4, 1, 2, 1, true, false, false, false, false, false, true>, p, pl.grid, s)) return rc;
   return oct_check_launch("igemm2 (fused backward)");
 }

@@ -25,32 +25,35 @@ struct RollParams {
   int tiles_x, tiles_y, ncols;
 };
 
-typedef unsigned int r3_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int r3_u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned r3_pack(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = (bf16_t)a;
-  v[1] = (bf16_t)b;
-  return __builtin_bit_cast(unsigned, v);
-}
+// The dynamic LDS of roll3d_kernel (byte offsets, each region starting where the one before it ends), for kernel and launcher
+template <int WM, int WN>
+struct Roll3dLds {
+  static constexpr int TH = 8, TW = 32, LH = TH + 2, LW = TW + 2, NPIX = LH * LW;
+  static constexpr int PIXB = 80, BUFB = NPIX * PIXB, NRING = 4, NT = WN * 32;
+  static constexpr int BUF = 0;                          // [NRING][BUFB] ring of halo tiles, one per slice
+  static constexpr int SXF = BUF + NRING * BUFB;         // float [2][32] scale, shift
+  static constexpr int OSCR = SXF + 64 * 4;              // [4 waves][32 px][80 B] epilogue scratch
+  static constexpr int WG_STATS = OSCR + 4 * 32 * 80;    // float [WM][2][NT]
+  static constexpr int BYTES = WG_STATS + WM * 2 * NT * 4;
+  static_assert((SXF | OSCR | WG_STATS | BYTES) % 16 == 0, "every region stays 16-B aligned");
+  static_assert(BYTES <= OCT_LDS_CAP, "LDS budget");
+};
 
 template <int WM, int WN, int MF, bool STATS>
 __global__ void __launch_bounds__(512) roll3d_kernel(const RollParams p) {
   static_assert(WM * WN == 4 && WM * MF == 8, "four MFMA waves, 8-row tiles");
-  constexpr int TH = 8, TW = 32, LH = TH + 2, LW = TW + 2, NPIX = LH * LW;
-  constexpr int NSLOT = (NPIX + 63) / 64, PIXB = 80, BUFB = NPIX * PIXB, NRING = 4;
-  constexpr int NT = WN * 32;
+  typedef Roll3dLds<WM, WN> L;
+  constexpr int TH = L::TH, TW = L::TW, LH = L::LH, LW = L::LW, NPIX = L::NPIX;
+  constexpr int NSLOT = (NPIX + 63) / 64, PIXB = L::PIXB, BUFB = L::BUFB, NT = L::NT;
   constexpr int KSTEPS = 54;   // (depth tap, tap, k16): s = kd * 18 + tap * 2 + k16
   typedef Mma<bf16_t> M;
   typedef M::Frag Frag;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* const buf0 = smem;
-  float* const sxf = reinterpret_cast<float*>(smem + NRING * BUFB);            // [2][32] scale, shift
-  unsigned char* const oscr = smem + NRING * BUFB + 64 * 4;                       // 4 waves x 32 px x 80 B
-  float* const wg_stats = reinterpret_cast<float*>(oscr + 4 * 32 * 80);          // [WM][2][NT]
+  unsigned char* const buf0 = smem + L::BUF;
+  float* const sxf = reinterpret_cast<float*>(smem + L::SXF);             // [2][32] scale, shift
+  unsigned char* const oscr = smem + L::OSCR;                             // 4 waves x 32 px x 80 B
+  float* const wg_stats = reinterpret_cast<float*>(smem + L::WG_STATS);   // [WM][2][NT]
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -70,7 +73,7 @@ __global__ void __launch_bounds__(512) roll3d_kernel(const RollParams p) {
     // =============================== producer waves ===============================
     const int ptid = tid - 256, grp = ptid & 3, pbase = ptid >> 2;
     constexpr int D = 2;
-    r3_u32x4 R[D][NSLOT];
+    u32x4 R[D][NSLOT];
     unsigned vmask[D];
     int relp[NSLOT];
     unsigned code[NSLOT];
@@ -100,7 +103,7 @@ __global__ void __launch_bounds__(512) roll3d_kernel(const RollParams p) {
       tyi = t % p.tiles_y; vol = t / p.tiles_y;
     };
     decode(i_col, i_txi, i_tyi, i_vol);
-    auto issue = [&](r3_u32x4 (&Rr)[NSLOT], unsigned& vm) {
+    auto issue = [&](u32x4 (&Rr)[NSLOT], unsigned& vm) {
       const int j = i_j, txi = i_txi, tyi = i_tyi, vol = i_vol;
       if (i_sidx < last) {
         ++i_sidx;
@@ -117,28 +120,28 @@ __global__ void __launch_bounds__(512) roll3d_kernel(const RollParams p) {
 #pragma unroll
       for (int i = 0; i < NSLOT; ++i) {
         const bool ok = zok && (code[i] & edge) == 0;
-        Rr[i] = *reinterpret_cast<const r3_u32x4*>(hb + (ok ? __umul24((unsigned)relp[i], cs2) : safe));
+        Rr[i] = *reinterpret_cast<const u32x4*>(hb + (ok ? __umul24((unsigned)relp[i], cs2) : safe));
         vm |= ok ? (1u << i) : 0u;
       }
     };
-    auto commit = [&](unsigned char* buf, const r3_u32x4 (&Rr)[NSLOT], unsigned vm) {
+    auto commit = [&](unsigned char* buf, const u32x4 (&Rr)[NSLOT], unsigned vm) {
 #pragma unroll
       for (int i = 0; i < NSLOT; ++i) {
         const int pix = pbase + 64 * i;
         if (pix < NPIX) {
-          r3_u32x4 v = Rr[i];
+          u32x4 v = Rr[i];
           if (p.xf) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const float lo = fmaxf(fmaf(__uint_as_float(v[j] << 16), s[2 * j], b[2 * j]), flo);
               const float hi = fmaxf(fmaf(__uint_as_float(v[j] & 0xffff0000u), s[2 * j + 1], b[2 * j + 1]), flo);
-              v[j] = r3_pack(lo, hi);
+              v[j] = pack_bf16x2(lo, hi);
             }
           }
           const bool live = (vm & (1u << i)) != 0;   // padding is exactly zero (it applies to the activated tensor)
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = live ? v[j] : 0u;
-          *reinterpret_cast<r3_u32x4*>(buf + pix * PIXB + grp * 16) = v;
+          *reinterpret_cast<u32x4*>(buf + pix * PIXB + grp * 16) = v;
         }
       }
     };
@@ -220,20 +223,20 @@ __global__ void __launch_bounds__(512) roll3d_kernel(const RollParams p) {
     unsigned char* sc = oscr + wave * (32 * 80);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const r3_u32x2 v = {packed[m][2 * g], packed[m][2 * g + 1]};
-      *reinterpret_cast<r3_u32x2*>(sc + r * 80 + (8 * g + 4 * hh) * 2) = v;   // pixel r, channels 8g + 4hh ..+3
+      const u32x2 v = {packed[m][2 * g], packed[m][2 * g + 1]};
+      *reinterpret_cast<u32x2*>(sc + r * 80 + (8 * g + 4 * hh) * 2) = v;   // pixel r, channels 8g + 4hh ..+3
     }
-    r3_u32x4 tv[2];
+    u32x4 tv[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int chunk = lane + 64 * k;   // 128 chunks of 16 B: pixel = chunk / 4, part = chunk % 4
-      tv[k] = *reinterpret_cast<const r3_u32x4*>(sc + (chunk >> 2) * 80 + (chunk & 3) * 16);
+      tv[k] = *reinterpret_cast<const u32x4*>(sc + (chunk >> 2) * 80 + (chunk & 3) * 16);
     }
     unsigned char* const fb = e_fb + (size_t)m * e_rowb;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int chunk = lane + 64 * k;
-      *reinterpret_cast<r3_u32x4*>(fb + (__umul24((unsigned)(chunk >> 2), e_pstep) + (unsigned)(chunk & 3) * 16u)) = tv[k];
+      *reinterpret_cast<u32x4*>(fb + (__umul24((unsigned)(chunk >> 2), e_pstep) + (unsigned)(chunk & 3) * 16u)) = tv[k];
     }
   };
   auto flush = [&]() {
@@ -283,8 +286,8 @@ __global__ void __launch_bounds__(512) roll3d_kernel(const RollParams p) {
       for (int m = 0; m < MF; ++m) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          packed[m][2 * q] = r3_pack(acc[m][4 * q], acc[m][4 * q + 1]);
-          packed[m][2 * q + 1] = r3_pack(acc[m][4 * q + 2], acc[m][4 * q + 3]);
+          packed[m][2 * q] = pack_bf16x2(acc[m][4 * q], acc[m][4 * q + 1]);
+          packed[m][2 * q + 1] = pack_bf16x2(acc[m][4 * q + 2], acc[m][4 * q + 3]);
         }
         if (STATS) {
 #pragma unroll
@@ -341,7 +344,7 @@ bool roll3d_plan(const OctConvDesc* d, ConvPlan* pl) {
 
 template <int WM, int WN, int MF, bool STATS>
 static int launch_roll(const RollParams& p, int grid, hipStream_t s) {
-  constexpr int lds = 4 * (10 * 34 * 80) + 64 * 4 + 4 * 32 * 80 + WM * 2 * (WN * 32) * 4;
+  constexpr int lds = Roll3dLds<WM, WN>::BYTES;
   if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&roll3d_kernel<WM, WN, MF, STATS>), lds)) return rc;
   hipLaunchKernelGGL((roll3d_kernel<WM, WN, MF, STATS>), dim3(grid), dim3(512), lds, s, p);
   return oct_check_launch("roll3d");

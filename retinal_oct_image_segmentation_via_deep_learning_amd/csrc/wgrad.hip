@@ -96,6 +96,15 @@ __device__ __forceinline__ void wg_fetch_dy8(const WgradParams& p, int img, int 
   }
 }
 
+// The dynamic LDS of wgrad_kernel<T, TR, KW> by esz = sizeof(T), tr and kw (byte offsets): the launcher picks the instantiation
+// at run time and takes its byte count from the same functions as the kernel
+struct WgradLds {
+  static constexpr int pixe(int esz) { return 32 + 8 / esz * 2; }  // elements per LDS pixel: 32 channels + pad (keeps 16-B rows)
+  static constexpr int in_tile() { return 0; }                      // T [(8 + tr - 1) * (32 + kw - 1)][pixe]
+  static constexpr int dy_tile(int esz, int tr, int kw) { return in_tile() + (8 + tr - 1) * (32 + kw - 1) * pixe(esz) * esz; }   // T [8 * 32][pixe]
+  static constexpr int bytes(int esz, int tr, int kw) { return dy_tile(esz, tr, kw) + 8 * 32 * pixe(esz) * esz; }
+};
+
 // One launch covers TR consecutive kernel rows (all KW columns) starting at row p.ty0: 3x3 = one launch of
 // <3,3>, 1x1 / deconv = <1,1>, ReLayNet's 7x3 = rows {0-2}, {3-5}, {6} -- the register budget (16 accumulators
 // per tap) caps a launch at 9 taps.  Input rows are staged with the matching vertical offset.
@@ -104,12 +113,14 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgradParams p) {
   constexpr int TAPS = TR * KW;
   constexpr int TH = 8, TW = 32;
   constexpr int LH = TH + TR - 1, LW = TW + KW - 1;
-  constexpr int PIXE = 32 + 8 / (int)sizeof(T) * 2;  // elements per LDS pixel: 32 channels + pad (keeps 16-B rows)
+  constexpr int PIXE = WgradLds::pixe((int)sizeof(T));
+  static_assert(WgradLds::dy_tile((int)sizeof(T), TR, KW) % 16 == 0, "every region stays 16-B aligned");
+  static_assert(WgradLds::bytes((int)sizeof(T), TR, KW) <= OCT_LDS_CAP, "LDS budget");
   typedef Mma<T> M;
   typedef typename M::Frag Frag;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* in_tile = reinterpret_cast<T*>(smem);                 // [LH*LW][PIXE]
-  T* dy_tile = in_tile + LH * LW * PIXE;                   // [TH*TW][PIXE]
+  T* in_tile = reinterpret_cast<T*>(smem + WgradLds::in_tile());                            // [LH*LW][PIXE]
+  T* dy_tile = reinterpret_cast<T*>(smem + WgradLds::dy_tile((int)sizeof(T), TR, KW));      // [TH*TW][PIXE]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
@@ -227,19 +238,18 @@ int launch_wgrad(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs*
   const dim3 grid(pl.grid, ceil_div(d->cout, 32), ceil_div(p.ktot, 32));
   p.part_mode = d->partials ? 1 : 0; p.slab_elems = (size_t)d->taps * d->cout * p.ktot; p.dbias_part = a->dbias_partials;
   const int esz = d->dtype == OCT_DT_BF16 ? 2 : 4;
-  const int pixe = 32 + 8 / esz * 2;
   p.pad_h = (kh - 1) / 2; p.pad_w = (kw - 1) / 2;
   const bool bf = d->dtype == OCT_DT_BF16;
   for (int ty0 = 0; ty0 < kh; ty0 += 3) {
     const int tr = kh - ty0 >= 3 ? 3 : 1;           // kh in {1, 3, 7}: groups of three rows, then single rows
     p.ty0 = ty0;
     if (ty0 > 0) p.dbias = nullptr;                  // the bias gradient belongs to one launch only
-    const size_t lds = (size_t)((8 + tr - 1) * (32 + kw - 1) + 8 * 32) * pixe * esz;
+    const int lds = WgradLds::bytes(esz, tr, kw);
     const auto kern = tr == 3 && kw == 3 ? (bf ? wgrad_kernel<bf16_t, 3, 3> : wgrad_kernel<float, 3, 3>)
                     : tr == 1 && kw == 3 ? (bf ? wgrad_kernel<bf16_t, 1, 3> : wgrad_kernel<float, 1, 3>)
                                          : (bf ? wgrad_kernel<bf16_t, 1, 1> : wgrad_kernel<float, 1, 1>);
     if (!bf)   // fp32 tiles exceed 64 KB
-      if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), 100 * 1024)) return rc;
+      if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(kern), OCT_LDS_CAP)) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
   }
   return oct_check_launch("wgrad");

@@ -46,15 +46,13 @@ extern "C" void oct_debug_set_trace_w2(void* buf) { g_trace_w2 = (unsigned long 
 #define W2TRACE(slot, idx) do {} while (0)
 #endif
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned w2_pack(float a, float b) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  bf16x2 v;
-  v[0] = (bf16_t)a;
-  v[1] = (bf16_t)b;
-  return __builtin_bit_cast(unsigned, v);
-}
+// The dynamic LDS of wgrad2_kernel<TAPS, CB, IB, TH> (bytes; each region starts where the one before it ends), for the kernel
+// and the launcher -- as functions, because the plan sizes its grid by the stage at run time (w2_grid)
+static constexpr int w2_inb(int taps, int th) { return (th + 2 * (taps == 9 ? 1 : 0)) * (32 + 2 * (taps != 1 ? 1 : 0)) * 64; }   // input tile of a 32-channel block
+static constexpr int w2_dyb(int th) { return th * 32 * 64; }                                                                     // dY tile of a 32-channel block
+static constexpr int w2_stage(int taps, int cb, int ib, int th) { return ib * w2_inb(taps, th) + cb * w2_dyb(th); }   // a stage: [ib] input tiles, [cb] dY tiles
+static constexpr int w2_sxf(int taps, int cb, int ib, int th) { return 2 * w2_stage(taps, cb, ib, th); }              // after the two stages: float [2][32 * ib]
+static constexpr int w2_lds(int taps, int cb, int ib, int th) { return w2_sxf(taps, cb, ib, th) + 2 * 32 * ib * (int)sizeof(float); }
 
 // D3: depth shift of the input tile / image map of an S2D dY (volumetric network) -- compile-time, see igemm2.hip
 // RSH: the nine taps are rows ty0 .. ty0 + 2 of a TALLER kernel (ReLayNet's 7x3, ReLayNet_2017.py:155-160, padding (3, 1)):
@@ -70,8 +68,11 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
   static_assert(TAPS != 3 || RSH, "the 1x3 kernel exists as a row group of a taller one");
   constexpr int LH = TH + 2 * HALO_Y, LW = TW + 2 * HALO;
   constexpr int NPI = LH * LW, NPD = TH * TW;          // pixels of the input / dY tile
-  constexpr int INB = NPI * 64, DYB = NPD * 64;        // bytes per 32-channel block
-  constexpr int STAGEB = IB * INB + CB * DYB;
+  constexpr int INB = w2_inb(TAPS, TH), DYB = w2_dyb(TH);        // bytes per 32-channel block
+  constexpr int STAGEB = w2_stage(TAPS, CB, IB, TH);
+  static_assert(INB == NPI * 64 && DYB == NPD * 64, "the layout's tiles are the kernel's");
+  static_assert(w2_sxf(TAPS, CB, IB, TH) % 16 == 0 && w2_lds(TAPS, CB, IB, TH) % 16 == 0, "every region stays 16-B aligned");
+  static_assert(w2_lds(TAPS, CB, IB, TH) <= OCT_LDS_CAP, "LDS budget");
   // W16 (3x3 kernels): v_mfma_f32_16x16x32_bf16 -- a fragment is 32 pixels (a whole tile row) x 16 channels, D = 16 co x 16 ci
   // in quarter S = 2*(co half) + (ci half) of the tap's accumulator: register 4S + e = (co 16a + 4*(lane>>4) + e, ci 16b + (lane&15)).
   // Same FLOPs, LDS reads and loop as the 32x32x16 form (pixel halves become channel halves); the chip holds a higher clock
@@ -95,6 +96,8 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
   typedef Mma<bf16_t> M;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* const stage0 = smem;                                                          // [2][STAGEB]
+  float* const sxf = reinterpret_cast<float*>(smem + w2_sxf(TAPS, CB, IB, TH));                // [2][32*IB]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int co_sb = blockIdx.y * (32 * CB), ci_sb = blockIdx.z * (32 * IB);
   int t0, tstep, nstage;
@@ -112,7 +115,6 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
   const int nstage_pad = (nstage + DRING - 1) / DRING * DRING;
 
   // BN scale/shift of this workgroup's input channels in LDS (kept off the in-order vmcnt queue)
-  float* const sxf = reinterpret_cast<float*>(smem + 2 * STAGEB);   // [2][32*IB]
   for (int i = tid; i < 32 * IB; i += 512) {
     const int cg = ci_sb + i;
     const bool second = cg >= p.c0;
@@ -259,7 +261,7 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
               for (int e = 0; e < 4; ++e) {
                 const float lo = fmaxf(fmaf(__uint_as_float(v[e] << 16), s[2 * e], b[2 * e]), flo);
                 const float hi = fmaxf(fmaf(__uint_as_float(v[e] & 0xffff0000u), s[2 * e + 1], b[2 * e + 1]), flo);
-                v[e] = w2_pack(lo, hi);
+                v[e] = pack_bf16x2(lo, hi);
               }
             }
             const bool live = ((S.vm[blk] >> j) & 1u) != 0;
@@ -285,7 +287,7 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
     const int last = nstage - 1;
 #pragma unroll
     for (int j = 0; j < D; ++j) issue(min(j, last), R[j]);
-    commit(smem, R[0]);
+    commit(stage0, R[0]);
     issue(min(D, last), R[0]);
     __syncthreads();
     // branch-free steady state over the padded stage count (see igemm2.hip)
@@ -294,7 +296,7 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
       for (int j = 0; j < D; ++j) {
         const int nx = s0 + j + 1;
         if (wave == 4) W2TRACE(4, nx - 1);
-        commit(smem + (nx & 1) * STAGEB, R[(j + 1) % D]);
+        commit(stage0 + (nx & 1) * STAGEB, R[(j + 1) % D]);
         if (wave == 4) W2TRACE(5, nx - 1);
         issue(min(nx + D, last), R[(j + 1) % D]);
         if (wave == 4) W2TRACE(6, nx - 1);
@@ -352,8 +354,8 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
   for (int s = 0; s < nstage_pad; ++s) {
     if (s >= nstage) { __syncthreads(); continue; }   // padded stages keep the barrier count in step
     if (wave == 0) W2TRACE(0, s);
-    const unsigned char* in_t = smem + cur * STAGEB + ib * INB + lane_off;
-    const unsigned char* dy_t = smem + cur * STAGEB + IB * INB + cb * DYB + lane_off;
+    const unsigned char* in_t = stage0 + cur * STAGEB + ib * INB + lane_off;
+    const unsigned char* dy_t = stage0 + cur * STAGEB + IB * INB + cb * DYB + lane_off;
     // flattened (row, half, tap) sequence with the transposed reads running two MFMAs ahead
     constexpr int NK = ROWS * 2;                 // k-steps (16 pixels) of this wave per stage
     auto a_off = [&](int k) { return ((psx * ROWS + (k >> 1)) * TW + (k & 1) * 16) * 64; };
@@ -374,8 +376,8 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
       };
       auto ao = [&](int k) { return W16 ? ((psx * ROWS + (k >> 1)) * TW) * 64 + (k & 1) * 32 : a_off(k); };
       // swizzled tiles: per-stage lane bases (the row / tap column of a fragment stays a compile-time DS offset)
-      const unsigned char* const in_b = smem + cur * STAGEB + ib * INB + (psx * ROWS) * LW * 64;
-      const unsigned char* const dy_b = smem + cur * STAGEB + IB * INB + cb * DYB + (psx * ROWS) * TW * 64;
+      const unsigned char* const in_b = stage0 + cur * STAGEB + ib * INB + (psx * ROWS) * LW * 64;
+      const unsigned char* const dy_b = stage0 + cur * STAGEB + IB * INB + cb * DYB + (psx * ROWS) * TW * 64;
       const unsigned char* in1[2] = {in_b + lo1[0], in_b + lo1[1]};
       const unsigned char* in2[2][2] = {{in_b + lo2[0][0], in_b + lo2[0][1]}, {in_b + lo2[1][0], in_b + lo2[1][1]}};
       const unsigned char* dy1[2] = {dy_b + lo1[0], dy_b + lo1[1]};
@@ -529,13 +531,10 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
 
 // Persistent grid of one launch: 2 workgroups per CU when the LDS allows (the row-shifted 7x3 launches call this per launch)
 struct W2Grid { int gx, per_wg, interleave; };
-static constexpr int w2_stage(int taps, int cb, int ib, int th) {
-  return ib * (th + 2 * (taps == 9 ? 1 : 0)) * (32 + 2 * (taps != 1 ? 1 : 0)) * 64 + cb * th * 32 * 64;
-}
 static W2Grid w2_grid(int taps, int cb, int ib, int th, int nco, int nci, int n, int h, int w) {
   const int ntiles = ((w + 31) / 32) * ((h + th - 1) / th) * n;
   W2Grid g;
-  g.gx = (2 * w2_stage(taps, cb, ib, th) * 2 <= 160 * 1024 ? 512 : 256) / ((nco / cb) * (nci / ib));
+  g.gx = (2 * w2_stage(taps, cb, ib, th) * 2 <= OCT_LDS_CAP ? 512 : 256) / ((nco / cb) * (nci / ib));
   if (g.gx < 1) g.gx = 1;
   if (g.gx > ntiles) g.gx = ntiles;
   g.per_wg = (ntiles + g.gx - 1) / g.gx;
@@ -546,7 +545,7 @@ static W2Grid w2_grid(int taps, int cb, int ib, int th, int nco, int nci, int n,
 
 template <int TAPS, int CB, int IB, int TH, bool RAGGED, bool D3 = false, bool RSH = false>
 static int launch_w2r(Wgrad2Params& p, int nco, int nci, hipStream_t s) {
-  constexpr int lds = 2 * w2_stage(TAPS, CB, IB, TH) + 2 * 32 * IB * (int)sizeof(float);
+  constexpr int lds = w2_lds(TAPS, CB, IB, TH);
   if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&wgrad2_kernel<TAPS, CB, IB, TH, RAGGED, D3, RSH>), lds)) return rc;
   const W2Grid g = w2_grid(TAPS, CB, IB, TH, nco, nci, p.n, p.h, p.w);
   p.tiles_x = (p.w + 31) / 32; p.tiles_y = (p.h + TH - 1) / TH; p.ntiles = p.tiles_x * p.tiles_y * p.n;
