@@ -715,6 +715,39 @@ size_t oct_contour_workspace_bytes(const OctContourDesc* d);
 int oct_contour_update(const OctContourDesc* d, const void* target, const void* pred, int64_t* records, void* workspace,
                        void* stream);
 
+/* Score evaluator (library 0.2.2, same OCT_VERSION): ONE launch per batch ADDS, per channel of a binary / multi-label head,
+ * the histogram of a 16-bit order-preserving key of every score, split by the element's label, to a device-resident state.
+ * ROC AUC (ties counted half), average precision and the confusion counts at every threshold follow from it on the host.
+ *   key16(v), v a non-NaN float32: the order-preserving code of v rounded toward -inf onto the bf16 grid.
+ *           u = bits(v), h = u >> 16, low = u & 0xFFFF
+ *           sign clear:  key = 0x8000 + h
+ *           sign set:    m = (h & 0x7FFF) + (low != 0), capped at 0x7F80;  key = 0x8000 - m
+ *           -0.0 and +0.0 share key 0x8000; keys lie in [0x0080, 0xFF80]; bin k is the half-open interval [g(k), g(k+1)) of the
+ *           real line, g(k) the bf16 value of code k.  For a threshold theta on the bf16 grid v >= theta <=> key16(v) >=
+ *           key16(theta) for every fp32 v, negative theta included (hence rounding toward -inf, not truncation); theta = 0 is
+ *           on the grid.  bf16 and uint8 scores convert to float32 exactly: one key space for all inputs.  No fp16.
+ *   target  uint8 [images][channels][h][w], values 0 / 1 (and ignore_value)
+ *   scores  the same shape, planar; score_elem OCT_SCORE_F32 / _BF16 / _U8
+ *   state   int64[oct_score_eval_state_elems(channels)], zeroed ONCE by the caller, C = channels:
+ *           hist[C][2][65536] | nan[C] | ignored[C] | invalid[C] | updates
+ *           Each element goes to exactly one place, decided in this order:
+ *             has_ignore and t == ignore_value -> ignored[c];  t > 1 -> invalid[c];  the score is NaN -> nan[c];
+ *             otherwise hist[c][t][key16(score)].   updates += 1 per call; images == 0 only counts the update.
+ * Counts gather in LDS; one 64-bit integer atomicAdd per non-zero bin and flush, integer atomics only: two runs give the same
+ * bits.  No allocation, no host synchronisation, only `stream`.  Any h, w >= 1 and any element-aligned base are accepted
+ * (16-byte loads only where base and plane size allow them); images * channels * h * w < 2^31.                          */
+#define OCT_SCORE_F32 0
+#define OCT_SCORE_BF16 1
+#define OCT_SCORE_U8 2
+typedef struct {
+  int images, h, w, channels; /* 1 <= channels <= OCT_MAX_CLASSES; images*channels*h*w < 2^31 */
+  int score_elem;             /* OCT_SCORE_* */
+  int has_ignore;
+  int ignore_value;           /* in [2,255], as oct_bce_loss_* */
+} OctScoreEvalDesc;
+size_t oct_score_eval_state_elems(int channels); /* channels*(2*65536 + 3) + 1; 0 for channels outside 1..16 */
+int oct_score_eval_update(const OctScoreEvalDesc* d, const uint8_t* target, const void* scores, int64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

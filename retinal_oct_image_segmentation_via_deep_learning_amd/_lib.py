@@ -83,6 +83,12 @@ class ContourDesc(C.Structure):      # struct OctContourDesc
                [("ignore_index", C.c_int64)]
 
 
+class ScoreEvalDesc(C.Structure):    # struct OctScoreEvalDesc
+    _fields_ = [(k, c_int) for k in ("images", "h", "w", "channels", "score_elem", "has_ignore", "ignore_value")]
+
+
+SCORE_F32, SCORE_BF16, SCORE_U8 = 0, 1, 2   # OCT_SCORE_*
+SCORE_KEYS = 65536   # hist[C][2][SCORE_KEYS] | nan[C] | ignored[C] | invalid[C] | updates
 CONTOUR_MAX_DIM = 16384   # h, w of oct_contour_update: keeps every squared distance below 2^31
 EVAL_PRED_U8, EVAL_PRED_I64, EVAL_PRED_NHWC_BF16, EVAL_PRED_NHWC_F32, EVAL_PRED_NCHW_F32 = range(5)   # OCT_EVAL_PRED_*
 EVAL_STATE_EXTRA = 4   # columns, ignored, invalid, updates behind cm [C*C] and thick_abs [C]
@@ -216,6 +222,8 @@ SIGNATURES = {
     "oct_seg_eval_update": (c_int, [C.POINTER(SegEvalDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
     "oct_contour_workspace_bytes": (c_size_t, [C.POINTER(ContourDesc)]),
     "oct_contour_update": (c_int, [C.POINTER(ContourDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_score_eval_state_elems": (c_size_t, [c_int]),
+    "oct_score_eval_update": (c_int, [C.POINTER(ScoreEvalDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

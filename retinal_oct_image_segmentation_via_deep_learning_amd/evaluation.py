@@ -39,6 +39,11 @@ int64 values on the device -- Hausdorff, HD95 and ASSD follow from them in `cont
                                ASSD = (sum_q[0] / n[0] + sum_q[1] / n[1]) / 2 / 2^17 (truncation <= 2^-17 px).  NaN unless
                                both sides have a point.
 
+Score evaluator (csrc/score_eval.hip, oct_score_eval_update): `ScoreEvaluator` validates a binary / multi-label (sigmoid) head
+without a threshold -- per channel one [2][65536] histogram of a 16-bit order-preserving key of the score by label, in one
+int64 device buffer; ROC AUC, average precision, the confusion counts at any threshold chosen afterwards and the best-Dice
+threshold follow from it in `score_metrics_from_state` (numpy, exact integers).  The key: `key16`.
+
 Deviations from the reference's Metrics/Contour_based_metrics.py, by decision: it scores only the FIRST contour find_contours
 returns (order-dependent) and counts the first vertex of a closed contour twice; here every contour counts and every vertex
 once.  For one simply connected object off the border hausdorff_distance is the same value, HD95 and ASSD differ by the weight
@@ -396,3 +401,329 @@ class BoundaryEvaluator:
         a side has no contour), defined [images, C] bool, mean_hausdorff / mean_hd95 / mean_assd [C] over the defined images
         (NaN without one), images."""
         return contour_metrics_from_records(self.records().cpu().numpy())
+
+
+# ---- score evaluator: ROC AUC, average precision and threshold sweeps per channel -------------------------------------------
+SCORE_KEYS = L.SCORE_KEYS
+_SCORE_ELEM = {torch.float32: L.SCORE_F32, torch.bfloat16: L.SCORE_BF16, torch.uint8: L.SCORE_U8}
+
+
+def score_state_size(channels: int) -> int:
+    return channels * (2 * SCORE_KEYS + 3) + 1
+
+
+def key16(v):
+    """The 16-bit key of float32 scores (numpy, any shape; the values must not be NaN): the order-preserving code of v rounded
+    toward -inf onto the bf16 grid.  With u = bits(v), h = u >> 16, low = u & 0xFFFF:
+      sign clear:  key = 0x8000 + h
+      sign set:    m = (h & 0x7FFF) + (low != 0), capped at 0x7F80;  key = 0x8000 - m
+    -0.0 and +0.0 share key 0x8000; keys lie in [0x0080, 0xFF80]; bin k is the half-open interval [g(k), g(k+1)) of the real
+    line, g = key_value.  For a threshold theta on the bf16 grid v >= theta <=> key16(v) >= key16(theta) for every fp32 v,
+    negative theta included (hence rounding toward -inf, not truncation); theta = 0 is on the grid."""
+    a = np.asarray(v, dtype=np.float32)
+    u = np.ascontiguousarray(a).reshape(-1).view(np.uint32).astype(np.int64).reshape(a.shape)
+    h, low = u >> 16, u & 0xFFFF
+    m = np.minimum((h & 0x7FFF) + (low != 0), 0x7F80)
+    return np.where(u >> 31 != 0, 0x8000 - m, 0x8000 + h)
+
+
+def key_value(k):
+    """g(k): the lower edge of bin k as float32 (the bf16 value whose key is k)"""
+    k = np.asarray(k, dtype=np.int64)
+    bits = np.where(k >= 0x8000, (k - 0x8000) << 16, 0x80000000 | ((0x8000 - k) << 16))
+    return bits.astype(np.uint32).view(np.float32)
+
+
+def _check_score_config(channels, ignore_value):
+    if isinstance(channels, bool) or not isinstance(channels, int):
+        raise TypeError(f"channels must be an int, got {type(channels).__name__} {channels!r}")
+    if not 1 <= channels <= L.MAX_CLASSES:
+        raise ValueError(f"channels must be in 1..{L.MAX_CLASSES} (got {channels})")
+    if ignore_value is not None and (isinstance(ignore_value, bool) or not isinstance(ignore_value, int)):
+        raise TypeError(f"ignore_value must be an int or None, got {type(ignore_value).__name__} {ignore_value!r}")
+    if ignore_value is not None and not 2 <= ignore_value <= 255:
+        raise ValueError(f"ignore_value {ignore_value} is not in [2, 255] (0 and 1 are the mask's own values)")
+
+
+def _score_hist(state, channels):
+    _check_score_config(channels, None)
+    s = np.asarray(state)
+    if s.dtype.kind not in "iu" or s.size != score_state_size(channels):
+        raise ValueError(f"state must hold {score_state_size(channels)} integers for {channels} channels, got {s.dtype} x {s.size}")
+    s = s.astype(np.int64).reshape(-1)
+    nh = channels * 2 * SCORE_KEYS
+    return s[:nh].reshape(channels, 2, SCORE_KEYS), s[nh:]
+
+
+def _threshold_keys(thresholds, logits):
+    from .losses import mask_threshold
+    theta = [mask_threshold(t) if logits else t for t in thresholds]
+    theta = np.array(theta, dtype=np.float32).reshape(-1)
+    if np.isnan(theta).any():
+        raise ValueError(f"thresholds must not be NaN, got {thresholds!r}")
+    return key16(theta)
+
+
+def _occupied(hist_c):
+    """occupied keys (ascending) of one channel with their counts as Python ints"""
+    neg, pos = hist_c[0], hist_c[1]
+    keys = np.flatnonzero((neg != 0) | (pos != 0))
+    return keys, [int(v) for v in neg[keys]], [int(v) for v in pos[keys]]
+
+
+def _pair_counts(neg, pos):
+    """P, N, sum_k pos_k neg_below_k and sum_k pos_k neg_k over the occupied keys in ascending order, as exact Python ints"""
+    below = wins = ties = 0
+    for n, p in zip(neg, pos):
+        wins += p * below
+        ties += p * n
+        below += n
+    return sum(pos), below, wins, ties
+
+
+def _auc_from_state(state):
+    """(auc | None, nan, invalid) of a one-channel state: the AUC alone, for Metrics.auc_score"""
+    hist, tail = _score_hist(state, 1)
+    _, neg, pos = _occupied(hist[0])
+    P, N, wins, ties = _pair_counts(neg, pos)
+    return ((2 * wins + ties) / (2 * P * N) if P and N else None), int(tail[0]), int(tail[2])
+
+
+def score_curves_from_state(state, channels: int, channel: int) -> dict:
+    """ROC and precision-recall points of one channel over its occupied keys in DESCENDING order (numpy, no GPU):
+    thresholds = key_value(key) float32, tp / fp = the counts of key >= that key (int64), tpr = tp / P, fpr = fp / N,
+    precision = tp / (tp + fp), recall = tpr.  NaN where a label is missing."""
+    hist, _ = _score_hist(state, channels)
+    if not 0 <= channel < channels:
+        raise ValueError(f"channel must be in 0..{channels - 1}, got {channel}")
+    keys, neg, pos = _occupied(hist[channel])
+    keys, neg, pos = keys[::-1], neg[::-1], pos[::-1]
+    tp, fp, a, b = [], [], 0, 0
+    for n, p in zip(neg, pos):
+        a, b = a + p, b + n
+        tp.append(a)
+        fp.append(b)
+    nan = float("nan")
+    return {
+        "thresholds": key_value(keys),
+        "tp": np.array(tp, dtype=np.int64), "fp": np.array(fp, dtype=np.int64),
+        "tpr": np.array([t / a if a else nan for t in tp], dtype=np.float64),
+        "fpr": np.array([f / b if b else nan for f in fp], dtype=np.float64),
+        "precision": np.array([t / (t + f) for t, f in zip(tp, fp)], dtype=np.float64),
+    }
+
+
+def score_metrics_from_state(state, channels: int, thresholds=(0.5,), logits=True) -> dict:
+    """Every figure of the score evaluator from its int64 state (numpy, no GPU), per channel.
+
+    With 16-bit scores (bf16 logits or probabilities, uint8 images) everything is exact.  With fp32 scores the counts at a
+    threshold theta are those at threshold_used <= theta (the lower edge of theta's bin; equal when theta is on the bf16 grid,
+    as 0 is), and the AUC is bracketed by [auc_lo, auc_hi], not exact: `auc` counts every pair inside one bin as a tie.
+
+      positives, negatives, nan, ignored, invalid   int64 [C];  updates int
+      auc                 (sum_k pos_k neg_below_k + 1/2 sum_k pos_k neg_k) / (P N): ties count half, sklearn's trapezoid.
+                          NaN unless both labels are present
+      auc_lo, auc_hi      the same with the tie term counted 0 and 1;  hi - lo = sum_k pos_k neg_k / (P N)
+      average_precision   sum_i (R_i - R_{i-1}) P_i over the occupied keys in descending order (sklearn); NaN without a positive
+      threshold_used [T]  float32 key_value(key16(theta)), theta = losses.mask_threshold(tau) with logits, float32(tau) without
+      counts [C, T, 6]    int64 tp, t, p, tn, fp, fn of key >= key16(theta), the argument order of Metrics._formulas;
+                          every key of Metrics._formulas as a float64 [C, T] array
+      best_dice, best_dice_threshold   the maximum of _formulas' Dice over all occupied keys as thresholds, and the largest
+                          threshold (float32) that attains it; NaN without an occupied key
+    Products of counts are exact Python integers (P N passes 2^63 on a real validation set); one float64 division ends each."""
+    import math
+    from .Metrics import _formulas
+    hist, tail = _score_hist(state, channels)
+    tkeys = _threshold_keys(thresholds, logits)
+    nt, nan = len(tkeys), float("nan")
+    res = {"nan": tail[:channels].copy(), "ignored": tail[channels:2 * channels].copy(),
+           "invalid": tail[2 * channels:3 * channels].copy(), "updates": int(tail[3 * channels]),
+           "positives": hist[:, 1].sum(axis=1), "negatives": hist[:, 0].sum(axis=1),
+           "threshold_used": key_value(tkeys)}
+    auc, lo, hi, ap = (np.full(channels, nan) for _ in range(4))
+    best, best_thr = np.full(channels, nan), np.full(channels, nan, dtype=np.float32)
+    counts = np.zeros((channels, nt, 6), dtype=np.int64)
+    for c in range(channels):
+        keys, neg, pos = _occupied(hist[c])
+        P, N, wins, ties = _pair_counts(neg, pos)
+        if P and N:
+            auc[c], lo[c], hi[c] = (2 * wins + ties) / (2 * P * N), wins / (P * N), (wins + ties) / (P * N)
+        # descending sweep: average precision and the best Dice
+        tp = fp = 0
+        terms = []
+        for k, n, p in zip(keys[::-1], neg[::-1], pos[::-1]):
+            tp, fp = tp + p, fp + n
+            terms.append((p * tp) / (tp + fp))
+            d = _formulas(tp, P, tp + fp, N - fp, fp, P - tp, P + N)["dice_coefficient"]
+            if not best[c] >= d:   # strictly better, or the first: ties keep the larger threshold
+                best[c], best_thr[c] = d, key_value(k)
+        if P:
+            ap[c] = math.fsum(terms) / P
+        above_pos = np.concatenate([np.cumsum(hist[c, 1][::-1])[::-1], [0]])
+        above_neg = np.concatenate([np.cumsum(hist[c, 0][::-1])[::-1], [0]])
+        for i, k in enumerate(tkeys):
+            tp, fp = int(above_pos[k]), int(above_neg[k])
+            counts[c, i] = (tp, P, tp + fp, N - fp, fp, P - tp)
+    res.update({"auc": auc, "auc_lo": lo, "auc_hi": hi, "average_precision": ap, "counts": counts,
+                "best_dice": best, "best_dice_threshold": best_thr})
+    n_all = res["positives"] + res["negatives"]
+    per = [[_formulas(*(int(v) for v in counts[c, i]), int(n_all[c])) for i in range(nt)] for c in range(channels)]
+    for k in _formulas(0, 0, 0, 0, 0, 0, 0):
+        res[k] = np.array([[per[c][i][k] for i in range(nt)] for c in range(channels)], dtype=np.float64).reshape(channels, nt)
+    return res
+
+
+class ScoreEvaluator:
+    """Threshold-free validation of a binary / multi-label head, accumulated on the device (csrc/score_eval.hip): per channel
+    ONE [2][65536] histogram of key16(score) by label in an int64 buffer
+
+        hist[C][2][65536] | nan[C] | ignored[C] | invalid[C] | updates
+
+    which every update() ADDS to with one kernel launch and no host synchronisation; compute() is the only call that reads it.
+    Each element goes to one place: ignored (ignore_value given and t == ignore_value), else invalid (t > 1), else nan (the
+    score is NaN), else hist[c][t][key16(score)].
+
+        ev = ScoreEvaluator(channels=3, ignore_value=255, logits=True)
+        for x, y in loader:
+            ev.update_model(model, x, y)        # or ev.update(y, scores, layout="nchw" | "nhwc")
+        ev.all_reduce()
+        m = ev.compute(thresholds=(0.5, 0.3))   # auc, average_precision, counts at any threshold, best_dice, ...
+
+    `logits` only decides how compute(thresholds=...) maps a probability threshold tau into score space: True through
+    losses.mask_threshold(tau) (predict_mask's rule), False as float32(tau).  What is exact and what is bracketed:
+    score_metrics_from_state."""
+
+    def __init__(self, channels, ignore_value=None, logits=True, device=None):
+        _check_score_config(channels, ignore_value)
+        self.channels = channels
+        self.ignore_value = ignore_value
+        self.logits = bool(logits)
+        self.device = torch.device(device) if device is not None else None
+        if self.device is not None and self.device.type != "cuda":
+            raise L.OctError("ScoreEvaluator needs a GPU device: there is no CPU fallback on the product path")
+        self.state = None   # int64 [C * (2 * 65536 + 3) + 1] on the device, allocated by the first update
+
+    def _state_on(self, device):
+        if device.type != "cuda":
+            raise L.OctError("the HIP path needs a device tensor (there is no CPU fallback)")
+        if self.state is None:
+            if self.device is not None and self.device.index is not None and device != self.device:
+                raise RuntimeError(f"inputs are on {device}, the evaluator was made for {self.device}")
+            self.state = torch.zeros(score_state_size(self.channels), dtype=torch.int64, device=device)
+        elif self.state.device != device:
+            raise RuntimeError(f"inputs are on {device}, the evaluator's state on {self.state.device}")
+        return self.state
+
+    def reset(self):
+        if self.state is not None:
+            self.state.zero_()
+        return self
+
+    def _launch(self, target, scores, images, h, w):
+        """target uint8 and scores, both contiguous [images][channels][h][w] on one device"""
+        state = self._state_on(target.device)
+        desc = L.ScoreEvalDesc(images, h, w, self.channels, _SCORE_ELEM[scores.dtype], int(self.ignore_value is not None),
+                               int(self.ignore_value or 0))
+        L.check(L.lib().oct_score_eval_update(C.byref(desc), target.data_ptr(), scores.data_ptr(), state.data_ptr(),
+                                              torch.cuda.current_stream(target.device).cuda_stream), "oct_score_eval_update")
+        return self
+
+    def update(self, target, scores, layout="nchw"):
+        """scores (B, C, H, W) fp32 / bf16 / uint8 ("nchw"; (B, H, W) is accepted for one channel) or (B, H, W, C) fp32 / bf16
+        ("nhwc": the logits networks' own output, taken through oct_nhwc_to_nchw to planar fp32 first -- an exact conversion,
+        so both layouts of the same values give the same state).  target: uint8 / bool (B, C, H, W), or (B, H, W) for one
+        channel (losses._binary_target's rules).  fp16 is refused: its mantissa does not fit the key."""
+        from .losses import _binary_target
+        if layout not in _LAYOUTS:
+            raise ValueError(f"layout must be 'nhwc' or 'nchw', got {layout!r}")
+        lay = _LAYOUTS[layout]
+        if not torch.is_tensor(scores):
+            raise TypeError(f"scores must be a torch tensor, got {type(scores).__name__}")
+        if scores.dtype == torch.bool:
+            scores = scores.view(torch.uint8)
+        if lay == L.SEG_NCHW and scores.dim() == 3 and self.channels == 1:
+            scores = scores.unsqueeze(1)
+        if scores.dim() != 4:
+            raise RuntimeError(f"expected 4-D scores, got {tuple(scores.shape)}")
+        if lay == L.SEG_NCHW:
+            if scores.dtype not in _SCORE_ELEM:
+                raise L.OctError(f"scores must be fp32, bf16 or uint8 (got {scores.dtype})")
+            n, c, h, w = scores.shape
+        else:
+            if scores.dtype not in (torch.bfloat16, torch.float32):
+                raise L.OctError(f"NHWC scores must be bf16 or fp32 (got {scores.dtype})")
+            n, h, w, c = scores.shape
+        if c != self.channels:
+            raise RuntimeError(f"the scores have {c} channels, the evaluator {self.channels}")
+        if h < 1 or w < 1:
+            raise RuntimeError(f"scores need H, W >= 1, got {tuple(scores.shape)}")
+        if n * c * h * w >= 2 ** 31:
+            raise RuntimeError(f"one update takes fewer than 2^31 elements, got {n} x {c} x {h} x {w}")
+        if scores.device.type != "cuda":
+            raise L.OctError("the HIP path needs a device tensor (there is no CPU fallback)")
+        target = _binary_target(target, n, c, h, w, scores.device)
+        scores = scores.detach().contiguous()
+        if lay == L.SEG_NHWC:
+            planar = torch.empty((n, c, h, w), dtype=torch.float32, device=scores.device)
+            if n:
+                dt = L.DT_BF16 if scores.dtype == torch.bfloat16 else L.DT_F32
+                L.check(L.lib().oct_nhwc_to_nchw(dt, scores.data_ptr(), planar.data_ptr(), n, c, h, w,
+                                                 torch.cuda.current_stream(scores.device).cuda_stream), "oct_nhwc_to_nchw")
+            scores = planar
+        return self._launch(target, scores, n, h, w)
+
+    @torch.no_grad()
+    def update_model(self, model, x, target):
+        """Forward of `model` in its current mode, then one update on its logits: the engine networks (UNet, BioUNet) through
+        model.logits(x) (NCHW fp32), the logits networks (SegLossMixin) through their NHWC logits.  UNet3D is refused: the
+        binary head is 2-D only."""
+        from .losses import SegLossMixin
+        from .unet import _EngineNet
+        if isinstance(model, SegLossMixin):
+            ncls, logits_net = model._classes(), True
+        elif isinstance(model, _EngineNet):
+            if not model._weighted_loss:
+                raise NotImplementedError(f"{type(model).__name__}: the binary / multi-label head is implemented for the 2-D "
+                                          "networks only")
+            ncls, logits_net = model._engine.ncls, False
+        else:
+            raise TypeError(f"update_model takes one of this package's networks, got {type(model).__name__}")
+        if ncls != self.channels:
+            raise RuntimeError(f"{type(model).__name__} has {ncls} output channels, the evaluator {self.channels}")
+        if not torch.is_tensor(x) or x.dim() != 4:
+            raise RuntimeError(f"expected a batched input (B, C, H, W), got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        want = (x.shape[0], ncls) + tuple(x.shape[2:])   # checked before the forward runs; update() applies the full rules
+        if not torch.is_tensor(target) or tuple(target.shape) not in ((want, (want[0],) + want[2:]) if ncls == 1 else (want,)):
+            raise RuntimeError(f"target must have shape {want}, got {tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
+        if logits_net:
+            return self.update(target, model._run_logits(x), "nhwc")
+        return self.update(target, model.logits(x), "nchw")
+
+    def all_reduce(self, group=None):
+        """Sum the state over the ranks of `group` (one SUM all-reduce of the int64 state); nothing to do in one process."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return self
+        if self.state is None:   # a rank without a batch still takes part
+            self._state_on(self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device()))
+        dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
+        return self
+
+    def _host_state(self):
+        if self.state is None:
+            return np.zeros(score_state_size(self.channels), dtype=np.int64)
+        return self.state.cpu().numpy()
+
+    def compute(self, thresholds=(0.5,)) -> dict:
+        """The only call that synchronises: score_metrics_from_state on the state, thresholds as probabilities."""
+        return score_metrics_from_state(self._host_state(), self.channels, thresholds, self.logits)
+
+    def roc_curve(self, channel=0):
+        """(fpr, tpr, thresholds) over the occupied keys in descending order; thresholds are key_value(key)"""
+        r = score_curves_from_state(self._host_state(), self.channels, channel)
+        return r["fpr"], r["tpr"], r["thresholds"]
+
+    def pr_curve(self, channel=0):
+        """(precision, recall, thresholds) over the occupied keys in descending order; thresholds are key_value(key)"""
+        r = score_curves_from_state(self._host_state(), self.channels, channel)
+        return r["precision"], r["tpr"], r["thresholds"]
