@@ -748,6 +748,73 @@ typedef struct {
 size_t oct_score_eval_state_elems(int channels); /* channels*(2*65536 + 3) + 1; 0 for channels outside 1..16 */
 int oct_score_eval_update(const OctScoreEvalDesc* d, const uint8_t* target, const void* scores, int64_t* state, void* stream);
 
+/* Paired image / label augmentation (library 0.2.2, same OCT_VERSION): ONE launch per batch warps the image, the label planes
+ * and the pixel-weight map of a batch with the same per-sample geometry and runs the intensity stages on the image.  A pure
+ * function of its inputs: (seed, step, sample_base + b) decide the noise, nothing else does.
+ *   Geometry, fixed point.  Pixel centres at integer coordinates; output pixel (xo, yo) of the ho x wo output reads the
+ *   hs x ws source at   SX = a*xo + b*yo + c + DX,   SY = d*xo + e*yo + f + DY   (Q24, evaluated in int64; sizes <= 8192).
+ *   a b d e are int32 Q24 (|value| < 128, 8 is plenty); c and f are int64 Q24, |value| < 2^40 -- the offset of a flip is
+ *   (ws - 1) * 2^24 and does not fit 32 bits.  Crop and resize are this map with ho x wo != hs x ws.
+ *   Elastic term (OCT_AUG_ELASTIC): disp int32 Q24 [batch][2][gh][gw] (plane 0 = DX, 1 = DY), |value| <= 64 * 2^24, on a
+ *   control grid of pitch P = grid_pitch = 2^k <= 1024; node (i, j) sits at output pixel (j*P, i*P), gw = ceil((wo-1)/P) + 1,
+ *   gh likewise.  With j = xo >> k, rx = xo & (P-1), i = yo >> k, ry = yo & (P-1):
+ *     top = n[i][j]*(P-rx) + n[i][j+1]*rx,  bot = n[i+1][j]*(P-rx) + n[i+1][j+1]*rx,  D = (top*(P-ry) + bot*ry) >> 2k
+ *   (arithmetic shift, int64; a node index past the grid only occurs with weight 0 and is clamped).
+ *   Sampling.  ix = SX >> 24, wx = ((SX >> 8) & 0xFFFF) * 2^-16; nearest index (SX + 2^23) >> 24; likewise for y.
+ *   image   src [batch][cin][hs][ws], uint8 / bf16 / fp32 (src_elem) -> out [batch][cin][ho][wo], bf16 / fp32 (out_elem):
+ *           v = (1-wy)*((1-wx)*p00 + wx*p01) + wy*((1-wx)*p10 + wx*p11), every multiply and add rounded to fp32 on its own
+ *           (no fma); a tap outside the source reads `fill` (finite).  Then, with the sample's parameters:
+ *             v = v*gain + bias                                   (two roundings)
+ *             OCT_AUG_GAMMA:  v = exp2(gamma * log2(min(max(v, 0), 1))), 0 -> 0          (v_log_f32 / v_exp_f32)
+ *             OCT_AUG_NOISE:  v = v*(1 + sigma_speckle*z1) + sigma_add*z2
+ *             v = min(max(v, out_lo), out_hi), rounded to out_elem (bf16: nearest even)
+ *           A stage whose flag is clear is skipped, not run with neutral values: without the two flags the path is exact.
+ *           Noise: Philox4x32-10, key (seed_lo, seed_hi), counter ((yo*wo + xo) >> 1, channel, sample_base + b, step); the even
+ *           pixel of a pair takes words 0,1, the odd one words 2,3:  u1 = ((w >> 9) + 0.5) * 2^-23, u2 = (w' >> 9) * 2^-23,
+ *           (z1, z2) = sqrt(-2 ln u1) * (cos, sin)(2 pi u2) on v_log_f32 / v_sqrt_f32 / v_cos_f32 / v_sin_f32.
+ *           cin == 0: no image (src / out may be null).
+ *   weight  optional fp32 [batch][hs][ws] -> weight_out [batch][ho][wo]: the same blend, outside taps read 0, no intensity.
+ *   labels  nearest, outside reads label_fill.  label_kind OCT_AUG_LABEL_CLASS_U8 / _CLASS_I64: class map [batch][hs][ws] ->
+ *           labels_out int64 [batch][ho][wo];  OCT_AUG_LABEL_MASK_U8: uint8 [batch][label_planes][hs][ws] -> uint8
+ *           [batch][label_planes][ho][wo], label_fill in [0, 255].
+ *   params  [batch][OCT_AUG_PARAM_WORDS] 32-bit words, 8-byte aligned, per sample:
+ *           [0..3] a b d e (int32)   [4,5] c, [6,7] f (int64, low word first)
+ *           [8..14] gain bias gamma sigma_speckle sigma_add out_lo out_hi (fp32)   [15] unused
+ * Every source index is clamped into its plane before the load.  Vector stores (8 - 16 B per thread) where wo % 4 == 0 and
+ * every output base is 16-byte aligned, element-wise stores otherwise: any wo, any element-aligned base, any batch up to
+ * 65535 samples.  No allocation, no synchronisation, only `stream`.  No z-score (it needs a reduction pass),
+ * no 3-D volumes.                                                                                                       */
+#define OCT_AUG_U8 0
+#define OCT_AUG_BF16 1
+#define OCT_AUG_F32 2
+#define OCT_AUG_LABEL_NONE 0
+#define OCT_AUG_LABEL_CLASS_U8 1
+#define OCT_AUG_LABEL_CLASS_I64 2
+#define OCT_AUG_LABEL_MASK_U8 3
+#define OCT_AUG_GAMMA 1
+#define OCT_AUG_NOISE 2
+#define OCT_AUG_ELASTIC 4
+#define OCT_AUG_PARAM_WORDS 16
+typedef struct {
+  int batch, cin;        /* cin may be 0 (labels / weight map only) */
+  int hs, ws, ho, wo;    /* 1..8192 each */
+  int src_elem;          /* OCT_AUG_U8 / _BF16 / _F32 */
+  int out_elem;          /* OCT_AUG_BF16 / _F32 */
+  int label_kind;        /* OCT_AUG_LABEL_* */
+  int label_planes;      /* planes of a mask; ignored for a class map */
+  int flags;             /* OCT_AUG_GAMMA | OCT_AUG_NOISE | OCT_AUG_ELASTIC */
+  int grid_pitch;        /* P, a power of two in [1, 1024]; read with OCT_AUG_ELASTIC only */
+  uint32_t seed_lo, seed_hi, step, sample_base;
+  float fill;
+  int reserved;
+  int64_t label_fill;
+} OctAugmentDesc;
+int oct_augment_pair(const OctAugmentDesc* d, const void* src, const void* labels, const float* weight, const void* params,
+                     const int32_t* disp, void* out, void* labels_out, float* weight_out, void* stream);
+/* out[i][0..3] = Philox4x32-10(counter = counters[i][0..3], key = (key_lo, key_hi)): the generator of oct_augment_pair, exported
+ * so that it can be pinned bit for bit.  n < 2^31.                                                                      */
+int oct_augment_philox_words(const uint32_t* counters, size_t n, uint32_t key_lo, uint32_t key_hi, uint32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,7 +87,19 @@ class ScoreEvalDesc(C.Structure):    # struct OctScoreEvalDesc
     _fields_ = [(k, c_int) for k in ("images", "h", "w", "channels", "score_elem", "has_ignore", "ignore_value")]
 
 
+class AugmentDesc(C.Structure):      # struct OctAugmentDesc
+    _fields_ = [(k, c_int) for k in ("batch", "cin", "hs", "ws", "ho", "wo", "src_elem", "out_elem", "label_kind", "label_planes",
+                                     "flags", "grid_pitch")] + \
+               [(k, C.c_uint32) for k in ("seed_lo", "seed_hi", "step", "sample_base")] + \
+               [("fill", c_float), ("reserved", c_int), ("label_fill", C.c_int64)]
+
+
 SCORE_F32, SCORE_BF16, SCORE_U8 = 0, 1, 2   # OCT_SCORE_*
+AUG_U8, AUG_BF16, AUG_F32 = 0, 1, 2   # OCT_AUG_* element kinds
+AUG_LABEL_NONE, AUG_LABEL_CLASS_U8, AUG_LABEL_CLASS_I64, AUG_LABEL_MASK_U8 = range(4)   # OCT_AUG_LABEL_*
+AUG_GAMMA, AUG_NOISE, AUG_ELASTIC = 1, 2, 4   # OCT_AUG_* flags
+AUG_PARAM_WORDS = 16   # 32-bit words per sample of oct_augment_pair's params
+AUG_MAX_DIM = 8192
 SCORE_KEYS = 65536   # hist[C][2][SCORE_KEYS] | nan[C] | ignored[C] | invalid[C] | updates
 CONTOUR_MAX_DIM = 16384   # h, w of oct_contour_update: keeps every squared distance below 2^31
 EVAL_PRED_U8, EVAL_PRED_I64, EVAL_PRED_NHWC_BF16, EVAL_PRED_NHWC_F32, EVAL_PRED_NCHW_F32 = range(5)   # OCT_EVAL_PRED_*
@@ -224,6 +236,9 @@ SIGNATURES = {
     "oct_contour_update": (c_int, [C.POINTER(ContourDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oct_score_eval_state_elems": (c_size_t, [c_int]),
     "oct_score_eval_update": (c_int, [C.POINTER(ScoreEvalDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_augment_pair": (c_int, [C.POINTER(AugmentDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
+    "oct_augment_philox_words": (c_int, [c_void_p, c_size_t, C.c_uint32, C.c_uint32, c_void_p, c_void_p]),
 }
 
 _lib = None
