@@ -815,6 +815,80 @@ int oct_augment_pair(const OctAugmentDesc* d, const void* src, const void* label
  * so that it can be pinned bit for bit.  n < 2^31.                                                                      */
 int oct_augment_philox_words(const uint32_t* counters, size_t n, uint32_t key_lo, uint32_t key_hi, uint32_t* out, void* stream);
 
+/* Connected components (library 0.2.2, same OCT_VERSION): multi-valued labelling of class maps [images][h][w], uint8 (elem 0) or
+ * int64 (elem 2), a cleanup filter on the components and streaming lesion-wise detection counts.  All integer arithmetic; every
+ * result is a pure function of the inputs: two runs give the same bits.
+ *   outside    a pixel whose value is not in [0, classes), or (has_ignore) equals ignore_index
+ *   connected  two inside pixels with the SAME value that are 4-neighbours (connectivity 4) or 8-neighbours (connectivity 8):
+ *              one pass labels every class; the background's components (the "holes") come with it
+ *
+ * oct_cc_label(d, map, roots, info, workspace, stream)
+ *   roots  int32 [images][h][w], WRITTEN: the smallest y*w + x of the pixel's component (its root); -1 for an outside pixel.
+ *          Independent of scheduling; ascending root order per class is the numbering of scipy.ndimage.label.
+ *   info   int32 [images][h][w], WRITTEN: at a root pixel area | (touches_border << 30), 0 everywhere else.  area < 2^29 since
+ *          h*w <= 2^28; touches_border: some pixel of the component lies in row 0, row h-1, column 0 or column w-1.
+ *
+ * oct_cc_filter(d, rules, map, roots, info, out, workspace, stream)
+ *   ONE pass over the components of the input (roots / info as oct_cc_label wrote them for `map` and `d`); no iteration to a
+ *   fixed point.  A component of class c is REPLACED when
+ *     area < min_area[c]  (0 = off; area == min_area is kept), or
+ *     keep_largest[c] and it is not the image's component of class c with the greatest area, ties to the smallest root (one
+ *       64-bit atomicMax per component on the key area << 32 | (0xFFFFFFFF - root): in LDS per workgroup, the workgroup's
+ *       maximum then into a per-(image, class) workspace slot), or
+ *     drop_enclosed[c] and it does not touch the border.
+ *   Replaced pixels get replace[c]; all other pixels, outside ones included, are copied.  `out` has the element type of `map` and
+ *   may be `map` itself.  Filling the holes of a binary mask: drop_enclosed[0] = 1, replace[0] = 1.  `rules` is host memory.
+ *
+ * oct_lesion_eval_update(d, target, pred, state, workspace, stream)        (streaming, like oct_seg_eval_update)
+ *   A pixel whose TARGET equals ignore_index is outside in BOTH maps (the rule of oct_contour_update): such a pixel splits a
+ *   predicted component that runs through it.  Both maps are labelled.  For a target component G of class c
+ *     inter(G) = #{pixels of G with pred == c};   G is DETECTED when inter(G) >= 1 and inter(G) * den >= num * area(G)
+ *   (num / den = overlap_num / overlap_den, the minimum overlap fraction, 0 <= num <= den, den >= 1; products in 64 bits).  A
+ *   predicted component is CONFIRMED by the same rule with the roles swapped.
+ *   state  int64 [classes][4] + 4, zeroed ONCE by the caller and ADDED to:
+ *          [c*4 + 0..3]   target components, predicted components, detected, confirmed of class c
+ *          [classes*4 +]  images, ignored pixels, invalid pixels (not ignored, t or p outside [0, classes)), updates
+ *
+ * workspace  oct_cc_workspace_bytes(d) bytes on the device for d->op, 16-byte aligned, contents irrelevant before and after.
+ *            With N = images*h*w and A(x) = x rounded up to 256:
+ *              OCT_CC_OP_LABEL   A(N)                               the classes as bytes
+ *              OCT_CC_OP_FILTER  A(N) + A(8*images*classes)         enough for a label and the filter behind it
+ *              OCT_CC_OP_LESION  2*A(N) + 6*A(4*N)                  bytes, roots, info and inter of both maps
+ *            0 for a descriptor that the entry points reject.  Each entry point uses the layout of its own op whatever d->op.
+ * oct_cc_tile  the tile (rows, columns) of the local pass: shapes that straddle tile borders follow from it.
+ * Launches: one workgroup per tile runs union-find in LDS (row runs by wave ballot) and writes every pixel's parent and each
+ * tile-local component's area; a border pass unites across the tile edges (and the diagonals, connectivity 8) with agent-scope
+ * atomicMin whose return value decides; a flatten pass writes the roots and adds the tile-local areas at the root.  No
+ * workgroup waits on another; parents only decrease, so every walk ends.  No allocation, no host synchronisation,
+ * integer atomics only, only `stream`.  Any h, w in 1..16384, any element-aligned base (read element-wise); images*h*w < 2^31. */
+#define OCT_CC_OP_LABEL 0
+#define OCT_CC_OP_FILTER 1
+#define OCT_CC_OP_LESION 2
+#define OCT_CC_BORDER_BIT 30 /* info: area | touches_border << 30 */
+typedef struct {
+  int images, h, w, classes; /* images = product of all leading dims; 1 <= classes <= 16; h, w <= 16384 */
+  int map_elem;              /* 0 uint8, 2 int64: the map (label, filter) or the target (lesion) */
+  int pred_elem;             /* 0 uint8, 2 int64: the prediction (lesion); 0 otherwise */
+  int connectivity;          /* 4 or 8 */
+  int op;                    /* OCT_CC_OP_*: which workspace oct_cc_workspace_bytes sizes */
+  int has_ignore;
+  int overlap_num, overlap_den; /* lesion: minimum overlap fraction, 0 <= num <= den, den >= 1 (0 / 1: any overlap) */
+  int reserved;
+  int64_t ignore_index;
+} OctCcDesc;
+typedef struct {
+  int min_area[OCT_MAX_CLASSES];      /* 0 = off */
+  int keep_largest[OCT_MAX_CLASSES];  /* 0 / 1 */
+  int drop_enclosed[OCT_MAX_CLASSES]; /* 0 / 1 */
+  int64_t replace[OCT_MAX_CLASSES];   /* uint8 maps: 0..255 */
+} OctCcRules;
+size_t oct_cc_workspace_bytes(const OctCcDesc* d);
+int oct_cc_tile(int* th, int* tw);
+int oct_cc_label(const OctCcDesc* d, const void* map, int32_t* roots, int32_t* info, void* workspace, void* stream);
+int oct_cc_filter(const OctCcDesc* d, const OctCcRules* rules, const void* map, const int32_t* roots, const int32_t* info, void* out,
+                  void* workspace, void* stream);
+int oct_lesion_eval_update(const OctCcDesc* d, const void* target, const void* pred, int64_t* state, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,20 @@ class AugmentDesc(C.Structure):      # struct OctAugmentDesc
                [("fill", c_float), ("reserved", c_int), ("label_fill", C.c_int64)]
 
 
+class CcDesc(C.Structure):           # struct OctCcDesc
+    _fields_ = [(k, c_int) for k in ("images", "h", "w", "classes", "map_elem", "pred_elem", "connectivity", "op", "has_ignore",
+                                     "overlap_num", "overlap_den", "reserved")] + \
+               [("ignore_index", C.c_int64)]
+
+
+class CcRules(C.Structure):          # struct OctCcRules
+    _fields_ = [("min_area", c_int * 16), ("keep_largest", c_int * 16), ("drop_enclosed", c_int * 16), ("replace", C.c_int64 * 16)]
+
+
+CC_OP_LABEL, CC_OP_FILTER, CC_OP_LESION = range(3)   # OCT_CC_OP_*
+CC_BORDER_BIT = 30     # info of a root: area | touches_border << 30
+CC_MAX_DIM = 16384     # h, w of the connected-component entry points
+LESION_STATE_EXTRA = 4   # images, ignored, invalid, updates behind [classes][4]
 SCORE_F32, SCORE_BF16, SCORE_U8 = 0, 1, 2   # OCT_SCORE_*
 AUG_U8, AUG_BF16, AUG_F32 = 0, 1, 2   # OCT_AUG_* element kinds
 AUG_LABEL_NONE, AUG_LABEL_CLASS_U8, AUG_LABEL_CLASS_I64, AUG_LABEL_MASK_U8 = range(4)   # OCT_AUG_LABEL_*
@@ -239,6 +253,11 @@ SIGNATURES = {
     "oct_augment_pair": (c_int, [C.POINTER(AugmentDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
     "oct_augment_philox_words": (c_int, [c_void_p, c_size_t, C.c_uint32, C.c_uint32, c_void_p, c_void_p]),
+    "oct_cc_workspace_bytes": (c_size_t, [C.POINTER(CcDesc)]),
+    "oct_cc_tile": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
+    "oct_cc_label": (c_int, [C.POINTER(CcDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_cc_filter": (c_int, [C.POINTER(CcDesc), C.POINTER(CcRules), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_lesion_eval_update": (c_int, [C.POINTER(CcDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

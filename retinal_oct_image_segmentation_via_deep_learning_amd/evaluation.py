@@ -44,6 +44,11 @@ without a threshold -- per channel one [2][65536] histogram of a 16-bit order-pr
 int64 device buffer; ROC AUC, average precision, the confusion counts at any threshold chosen afterwards and the best-Dice
 threshold follow from it in `score_metrics_from_state` (numpy, exact integers).  The key: `key16`.
 
+Lesion-wise scores (csrc/components.hip, oct_lesion_eval_update): `LesionEvaluator` labels both maps into connected components
+(same value, 4- or 8-neighbours; postprocess.py has the labelling itself and the cleanup filter) and keeps, per class, four
+int64 counts on the device -- target components, predicted components, detected, confirmed; sensitivity, precision and F1 per
+lesion follow from them in `lesion_metrics_from_state` (numpy, float64).
+
 Deviations from the reference's Metrics/Contour_based_metrics.py, by decision: it scores only the FIRST contour find_contours
 returns (order-dependent) and counts the first vertex of a closed contour twice; here every contour counts and every vertex
 once.  For one simply connected object off the border hausdorff_distance is the same value, HD95 and ASSD differ by the weight
@@ -727,3 +732,168 @@ class ScoreEvaluator:
         """(precision, recall, thresholds) over the occupied keys in descending order; thresholds are key_value(key)"""
         r = score_curves_from_state(self._host_state(), self.channels, channel)
         return r["precision"], r["tpr"], r["thresholds"]
+
+
+# ---- lesion-wise scores: detection counts over connected components ----------------------------------------------------------
+LESION_FIELDS = ("target_components", "pred_components", "detected", "confirmed")
+
+
+def lesion_state_size(classes: int) -> int:
+    return classes * len(LESION_FIELDS) + L.LESION_STATE_EXTRA
+
+
+def _check_overlap(min_overlap):
+    if not isinstance(min_overlap, (tuple, list)) or len(min_overlap) != 2:
+        raise TypeError(f"min_overlap must be a pair of ints (num, den), got {min_overlap!r}")
+    num, den = min_overlap
+    for v in (num, den):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"min_overlap must be a pair of ints (num, den), got {min_overlap!r}")
+    if not (1 <= den < 2 ** 31 and 0 <= num <= den):
+        raise ValueError(f"min_overlap must be a fraction num / den in [0, 1] with 1 <= den < 2^31, got {num} / {den}")
+    return num, den
+
+
+def lesion_metrics_from_state(state, classes: int) -> dict:
+    """The lesion-wise figures of LesionEvaluator from its int64 state (numpy float64, no GPU), per class:
+      target_components, pred_components, detected, confirmed   int64 [C]
+      sensitivity = detected / target_components, precision = confirmed / pred_components,
+      f1 = 2 sensitivity precision / (sensitivity + precision)   float64 [C]; a 0 / 0 is NaN, f1 is NaN where either is NaN and 0
+      where both are 0;   images, ignored, invalid, updates   int."""
+    _check_config(classes, None)
+    s = np.asarray(state)
+    if s.dtype.kind not in "iu" or s.size != lesion_state_size(classes):
+        raise ValueError(f"state must hold {lesion_state_size(classes)} integers for {classes} classes, got {s.dtype} x {s.size}")
+    s = s.astype(np.int64).reshape(-1)
+    counts = s[:classes * 4].reshape(classes, 4)
+    nt, npred, det, conf = (counts[:, k].copy() for k in range(4))
+    nan = np.float64("nan")
+    sens = np.where(nt > 0, det / np.where(nt > 0, nt, 1), nan)
+    prec = np.where(npred > 0, conf / np.where(npred > 0, npred, 1), nan)
+    both = sens + prec                                     # NaN where either is
+    f1 = np.where(both > 0, 2.0 * sens * prec / np.where(both > 0, both, 1.0), np.where(both == 0, 0.0, nan))
+    images, ignored, invalid, updates = (int(v) for v in s[classes * 4:])
+    return {"target_components": nt, "pred_components": npred, "detected": det, "confirmed": conf,
+            "sensitivity": sens, "precision": prec, "f1": f1,
+            "images": images, "ignored": ignored, "invalid": invalid, "updates": updates}
+
+
+class LesionEvaluator:
+    """Lesion-wise detection scores of a validation set (csrc/components.hip, oct_lesion_eval_update): both maps are labelled
+    into connected components (same value, 4- or 8-neighbours); a target component G of class c is DETECTED when
+    inter(G) = #{pixels of G with pred == c} >= 1 and inter(G) * den >= num * area(G), num / den = min_overlap; a predicted
+    component is CONFIRMED by the same rule with the roles swapped.  A pixel whose target equals ignore_index is outside in both
+    maps, so it splits a predicted component that runs through it.  One int64 device buffer
+
+        [classes][target_components, pred_components, detected, confirmed] | images | ignored | invalid | updates
+
+    which every update() ADDS to without a host synchronisation; compute() is the only call that reads it.  A batch goes through
+    the kernels in chunks of images whose workspace (26 bytes per pixel) fits max_workspace_bytes."""
+
+    def __init__(self, classes, connectivity=4, ignore_index=None, min_overlap=(0, 1), device=None, max_workspace_bytes=256 << 20):
+        _check_config(classes, ignore_index)
+        if isinstance(connectivity, bool) or connectivity not in (4, 8):
+            raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+        if isinstance(max_workspace_bytes, bool) or not isinstance(max_workspace_bytes, int) or max_workspace_bytes < 1:
+            raise ValueError(f"max_workspace_bytes must be a positive int, got {max_workspace_bytes!r}")
+        self.min_overlap = _check_overlap(min_overlap)
+        self.classes = classes
+        self.connectivity = connectivity
+        self.ignore_index = ignore_index
+        self.max_workspace_bytes = max_workspace_bytes
+        self.device = torch.device(device) if device is not None else None
+        if self.device is not None and self.device.type != "cuda":
+            raise L.OctError("LesionEvaluator needs a GPU device: there is no CPU fallback on the product path")
+        self.state = None        # int64 [C*4 + 4] on the device, allocated by the first update
+        self._workspace = None   # uint8 device buffer, grown on demand, reused by every update
+
+    def _state_on(self, device):
+        if device.type != "cuda":
+            raise L.OctError("the HIP path needs a device tensor (there is no CPU fallback)")
+        if self.state is None:
+            if self.device is not None and self.device.index is not None and device != self.device:
+                raise RuntimeError(f"inputs are on {device}, the evaluator was made for {self.device}")
+            self.state = torch.zeros(lesion_state_size(self.classes), dtype=torch.int64, device=device)
+        elif self.state.device != device:
+            raise RuntimeError(f"inputs are on {device}, the evaluator's state on {self.state.device}")
+        return self.state
+
+    def reset(self):
+        if self.state is not None:
+            self.state.zero_()
+        return self
+
+    def _desc(self, images, h, w, target, pred):
+        return L.CcDesc(images, h, w, self.classes, 0 if target.dtype == torch.uint8 else 2, 0 if pred.dtype == torch.uint8 else 2,
+                        self.connectivity, L.CC_OP_LESION, int(self.ignore_index is not None), self.min_overlap[0],
+                        self.min_overlap[1], 0, int(self.ignore_index or 0))
+
+    def update(self, target, pred):
+        """Two integer class maps of one shape (..., H, W), H, W <= 16384, with SegEvaluator.update's input rules.  One image
+        whose workspace does not fit max_workspace_bytes raises.  Nothing is read back."""
+        target, pred = _class_map(target, "target"), _class_map(pred, "pred")
+        if target.shape != pred.shape:
+            raise RuntimeError(f"target {tuple(target.shape)} and pred {tuple(pred.shape)} must have the same shape")
+        if target.device != pred.device:
+            raise RuntimeError(f"target is on {target.device}, pred on {pred.device}")
+        h, w = target.shape[-2:]
+        if h < 1 or w < 1:
+            raise RuntimeError(f"class maps need H, W >= 1, got {tuple(target.shape)}")
+        if h > L.CC_MAX_DIM or w > L.CC_MAX_DIM:
+            raise RuntimeError(f"connected components take H, W <= {L.CC_MAX_DIM}, got {h} x {w}")
+        state = self._state_on(target.device)
+        images = target.numel() // (h * w)
+        if images == 0:
+            return self
+        lib = L.lib()
+        one = int(lib.oct_cc_workspace_bytes(C.byref(self._desc(1, h, w, target, pred))))
+        if one == 0:
+            raise L.OctError(f"oct_cc_workspace_bytes failed: {L.last_error()}")
+        if one > self.max_workspace_bytes:
+            raise RuntimeError(f"one {h} x {w} image needs a workspace of {one} bytes, max_workspace_bytes is "
+                               f"{self.max_workspace_bytes}")
+        per = min(images, self.max_workspace_bytes // one, max(1, (2 ** 31 - 1) // (h * w)))   # bytes(k) <= k * bytes(1)
+        target, pred = target.reshape(images, h, w), pred.reshape(images, h, w)
+        stream = torch.cuda.current_stream(target.device).cuda_stream
+        for lo in range(0, images, per):
+            k = min(per, images - lo)
+            desc = self._desc(k, h, w, target, pred)
+            need = int(lib.oct_cc_workspace_bytes(C.byref(desc)))
+            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != target.device:
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=target.device)
+            L.check(lib.oct_lesion_eval_update(C.byref(desc), target[lo:lo + k].data_ptr(), pred[lo:lo + k].data_ptr(),
+                                               state.data_ptr(), self._workspace.data_ptr(), stream), "oct_lesion_eval_update")
+        return self
+
+    @torch.no_grad()
+    def update_model(self, model, x, target):
+        """model.predict(x) of one of this package's networks in its current mode against target: the engine networks (UNet,
+        BioUNet, UNet3D -- a (B, D, H, W) map counts B*D slice images) and the logits networks (SegLossMixin) alike."""
+        from .losses import SegLossMixin
+        from .unet import _EngineNet
+        if isinstance(model, SegLossMixin):
+            ncls = model._classes()
+        elif isinstance(model, _EngineNet):
+            ncls = model._engine.ncls
+        else:
+            raise TypeError(f"update_model takes one of this package's networks, got {type(model).__name__}")
+        if ncls != self.classes:
+            raise RuntimeError(f"{type(model).__name__} has {ncls} classes, the evaluator {self.classes}")
+        return self.update(target, model.predict(x))
+
+    def all_reduce(self, group=None):
+        """Sum the state over the ranks of `group` (one all-reduce of C*4 + 4 int64); nothing to do in one process."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return self
+        if self.state is None:   # a rank without a batch still takes part
+            self._state_on(self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device()))
+        dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
+        return self
+
+    def compute(self) -> dict:
+        """The only call that synchronises: lesion_metrics_from_state on the state.  `updates` counts kernel calls, one per
+        chunk of an update."""
+        if self.state is None:
+            return lesion_metrics_from_state(np.zeros(lesion_state_size(self.classes), dtype=np.int64), self.classes)
+        return lesion_metrics_from_state(self.state.cpu().numpy(), self.classes)
