@@ -170,10 +170,14 @@ typedef struct OctWgradArgs {
   const void* dy;
   float* dwp;
   float* dbias; /* optional: += sum over pixels of dy per real output channel (bias gradient); caller zeroes */
-  /* optional fused BatchNorm-backward apply (first layer only, OCT_E_INVALID elsewhere): when dy_coef != NULL,
+  /* optional fused BatchNorm-backward apply (first layer, or with dy_out below; OCT_E_INVALID elsewhere): when dy_coef != NULL,
    * `dy` holds dA and the kernel forms dy = coef0*[y*scale+shift>0]*dA + coef1*y + coef2 on the fly */
   const void* dy_y; const float* dy_coef; const float* dy_scale; const float* dy_shift;
   float* dbias_partials; /* partials mode with dbias != NULL: [slabs][cout] fp32 (GEMM rows, i.e. 4*Cout for the deconv) */
+  /* optional, with dy_coef (where oct_conv_wgrad_apply_store_ok says 1, OCT_E_INVALID elsewhere): the dY the kernel forms is
+   * also stored here, [n,h,w,cout] in bf16 -- bit for bit what oct_bn_bwd_apply_to(dy_out, dy, dy_y, dy_coef, dy_scale,
+   * dy_shift) writes -- for the data gradient that runs next.  dy_out == dy is allowed.  No dbias in this form. */
+  void* dy_out;
 } OctWgradArgs;
 int oct_conv_wgrad(const OctWgradDesc* d, const OctWgradArgs* a, void* stream);
 /* slabs a launch of this descriptor writes when partials = 1 (host query, never fails; >= 1) */
@@ -185,6 +189,11 @@ int oct_reduce_bias_partials(const float* part, int nparts, int rows, int channe
 /* 1 when oct_conv_wgrad accepts dy_coef (fused BatchNorm-backward apply) for this descriptor, else 0: the
  * caller then materialises dY with oct_bn_bwd_apply first.  Host-only query, never fails.               */
 int oct_conv_wgrad_fused_apply_ok(const OctWgradDesc* d);
+/* 1 when oct_conv_wgrad accepts dy_coef together with dy_out for this descriptor (the pipelined 3x3 kernel applies the
+ * BatchNorm backward when it stages dY and stores dY for the data gradient: no oct_bn_bwd_apply launch, one read of the
+ * tensor less): bf16, plain dY, whole tiles (W % 32, H % 8), partials == 0, and a launch grid of a single channel column --
+ * Cout = 32 with 64 input channels.  Host-only query, never fails.                                         */
+int oct_conv_wgrad_apply_store_ok(const OctWgradDesc* d);
 /* 1 when oct_conv_wgrad accepts in_img_shift = OCT_IMG_SHIFT_ALL for this descriptor (nn.Conv3d(1, F, 3) weight gradient,
  * engine3d: all 27 taps in one pass over dY instead of three), else 0.  Host-only query, never fails.    */
 int oct_conv_wgrad_all_depth_taps_ok(const OctWgradDesc* d);
@@ -365,6 +374,24 @@ int oct_head_backward_fused(const OctHeadDesc* d, const void* y, const float* sc
                             const int64_t* target, const float* dice_coef, float w_ce,
                             const float* dprobs, void* dlogits, void* da, float* partials,
                             float* dbias, float* dweight, double* loss_partials, void* stream);
+/* The matrix-pipe head backward without the dA round trip.  dA = W^T dlogits is a function of the <= 8 bf16 numbers
+ * dlogits[pixel][*], so the head can hand those 16 B per pixel to the BatchNorm backward of the layer below instead of
+ * the 64-B dA row, and the apply pass recomputes dA (same code, same bits) while it reads y.
+ *   oct_head_backward_dl_ok : 1 exactly where oct_head_backward_fused runs on the matrix pipe: bf16, feat 32,
+ *                             classes <= 8, OCT_HEAD_MFMA not 0.
+ *   oct_head_backward_dl    : oct_head_backward_fused (labels, fused dweight -- both required) with dl8 in place of da:
+ *                             dl8 [npix][8] in bf16, slots >= classes zero.  partials, dbias, dweight and
+ *                             loss_partials as there (same grid, oct_head_blocks; the partial rows are bit-identical).
+ *   oct_head_bwd_apply      : dy = coef0*([y*scale+shift > 0] ? bf16(W^T dl) : 0) + coef1*y + coef2, [npix][32] in bf16.
+ * oct_head_backward_dl + oct_head_bwd_apply give the bits of oct_head_backward_fused(da) + oct_bn_bwd_apply(da, y, coef,
+ * scale, shift).  Not eligible -> OCT_E_INVALID, nothing written.                                                      */
+int oct_head_backward_dl_ok(const OctHeadDesc* d);
+int oct_head_backward_dl(const OctHeadDesc* d, const void* y, const float* scale, const float* shift,
+                         const float* mean, const float* invstd, const float* w, const float* b,
+                         const int64_t* target, const float* dice_coef, float w_ce, void* dl8, float* partials,
+                         float* dbias, float* dweight, double* loss_partials, void* stream);
+int oct_head_bwd_apply(const OctHeadDesc* d, const void* dl8, const void* y, const float* scale, const float* shift,
+                       const float* w, const float* coef /* [3][32] */, void* dy, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Segmentation loss on logits a network has already produced (U_Net / AttU_Net / AttU_Net4,

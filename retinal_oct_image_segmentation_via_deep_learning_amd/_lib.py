@@ -62,7 +62,7 @@ class WgradDesc(C.Structure):
 
 class WgradArgs(C.Structure):
     _fields_ = [(k, c_void_p) for k in ("x0", "x1", "scale0", "shift0", "scale1", "shift1", "dy", "dwp", "dbias",
-                                                "dy_y", "dy_coef", "dy_scale", "dy_shift", "dbias_partials")]
+                                                "dy_y", "dy_coef", "dy_scale", "dy_shift", "dbias_partials", "dy_out")]
 
 
 class ConvBwdFusedArgs(C.Structure):   # struct OctConvBwdFusedArgs
@@ -154,6 +154,7 @@ SIGNATURES = {
     "oct_conv_forward": (c_int, [C.POINTER(ConvDesc), C.POINTER(ConvArgs), c_void_p]),
     "oct_conv_wgrad": (c_int, [C.POINTER(WgradDesc), C.POINTER(WgradArgs), c_void_p]),
     "oct_conv_wgrad_fused_apply_ok": (c_int, [C.POINTER(WgradDesc)]),
+    "oct_conv_wgrad_apply_store_ok": (c_int, [C.POINTER(WgradDesc)]),
     "oct_conv_wgrad_all_depth_taps_ok": (c_int, [C.POINTER(WgradDesc)]),
     "oct_conv_backward_fused_ok": (c_int, [C.POINTER(WgradDesc)]),
     "oct_conv_backward_fused_blocks": (c_int, [C.POINTER(WgradDesc)]),
@@ -199,6 +200,12 @@ SIGNATURES = {
     "oct_head_backward_fused": (c_int, [C.POINTER(HeadDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_head_backward_dl_ok": (c_int, [C.POINTER(HeadDesc)]),
+    "oct_head_backward_dl": (c_int, [C.POINTER(HeadDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    "oct_head_bwd_apply": (c_int, [C.POINTER(HeadDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
     "oct_seg_loss_blocks": (c_int, [c_size_t, c_int]),
     "oct_seg_loss_forward": (c_int, [C.POINTER(HeadDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oct_seg_loss_backward": (c_int, [C.POINTER(HeadDesc), c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,

@@ -69,6 +69,7 @@ struct WgradPlan {
 bool first_wgrad_plan(const OctWgradDesc* d, bool dbias, bool dy_coef, WgradPlan* pl);   // first.hip
 bool wgrad2_plan(const OctWgradDesc* d, WgradPlan* pl);                                  // wgrad2.hip
 void wgrad_plan(const OctWgradDesc* d, WgradPlan* pl);                                   // wgrad.hip: generic
+bool wgrad2_apply_store_ok(const OctWgradDesc* d, const WgradPlan& pl);   // wgrad2.hip: BatchNorm-backward apply on load + dY store
 int launch_first_wgrad(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s);
 int launch_wgrad2(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s);
 int launch_wgrad(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s);

@@ -96,6 +96,15 @@ extern "C" int oct_conv_wgrad_fused_apply_ok(const OctWgradDesc* d) {
   return d && d->kh != 7 && plan_conv_wgrad(d, false, false).path == WGRAD_FIRST;
 }
 
+// Host query behind OctWgradArgs.dy_coef + dy_out: the wgrad2 launch of this descriptor can apply the BatchNorm backward on
+// load and store dY for the data gradient (wgrad2_apply_store_ok holds the conditions, next to the kernel they describe)
+extern "C" int oct_conv_wgrad_apply_store_ok(const OctWgradDesc* d) {
+  int kh, kw;
+  if (!d || d->dtype != OCT_DT_BF16 || !kernel_size(d->taps, d->kh, d->kw, &kh, &kw)) return 0;
+  if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c0 <= 0 || d->c1 < 0 || d->cout <= 0) return 0;
+  return wgrad2_apply_store_ok(d, plan_conv_wgrad(d, false, false)) ? 1 : 0;
+}
+
 // Host query: 1 when oct_conv_wgrad accepts in_img_shift = OCT_IMG_SHIFT_ALL for this descriptor (all three depth taps of a
 // Conv3d(1 -> F) weight gradient in one launch, dwp = [3][9][cout]); else the caller launches once per depth tap.
 extern "C" int oct_conv_wgrad_all_depth_taps_ok(const OctWgradDesc* d) {
@@ -126,8 +135,14 @@ extern "C" int oct_conv_wgrad(const OctWgradDesc* d, const OctWgradArgs* a, void
   OCT_CHECK(!(d->xform0 && (!a->scale0 || !a->shift0)), "oct_conv_wgrad: xform0 without scale/shift");
   OCT_CHECK(!(d->xform1 && (!a->scale1 || !a->shift1)), "oct_conv_wgrad: xform1 without scale/shift");
   OCT_CHECK(!d->partials || !a->dbias || a->dbias_partials, "oct_conv_wgrad: partials mode with a bias gradient needs dbias_partials");
-  const WgradPlan pl = plan_conv_wgrad(d, a->dbias != nullptr, a->dy_coef != nullptr);
-  OCT_CHECK(!a->dy_coef || pl.path == WGRAD_FIRST, "oct_conv_wgrad: the fused BN-backward apply is only implemented for the 1->F first layer in bf16");
+  // dy_coef with dy_out: the pipelined 3x3 kernel applies the BatchNorm backward on load and stores dY (wgrad2.hip, DYAPPLY)
+  const bool apply_store = a->dy_coef && a->dy_out;
+  OCT_CHECK(!a->dy_out || a->dy_coef, "oct_conv_wgrad: dy_out goes with dy_coef");
+  OCT_CHECK(!apply_store || oct_conv_wgrad_apply_store_ok(d),
+            "oct_conv_wgrad: dy_coef + dy_out is not available for this descriptor (oct_conv_wgrad_apply_store_ok)");
+  OCT_CHECK(!apply_store || !a->dbias, "oct_conv_wgrad: dy_coef + dy_out takes no bias gradient");
+  const WgradPlan pl = plan_conv_wgrad(d, a->dbias != nullptr, a->dy_coef != nullptr && !apply_store);
+  OCT_CHECK(!a->dy_coef || apply_store || pl.path == WGRAD_FIRST, "oct_conv_wgrad: the fused BN-backward apply is only implemented for the 1->F first layer in bf16");
   OCT_CHECK(!a->dy_coef || (a->dy_y && a->dy_scale && a->dy_shift), "oct_conv_wgrad: fused apply needs y, scale, shift");
   if (d->partials) {   // the caller sized dwp from oct_conv_wgrad_partials, which plans without the launch's arguments
     const int slabs = plan_conv_wgrad(d, false, false).slabs;

@@ -10,8 +10,10 @@
 #define HEAD_THREADS 256
 int oct_head_backward_mfma(const OctHeadDesc* d, const void* y, const float* scale, const float* shift, const float* mean,
                            const float* invstd, const float* w, const float* b, const int64_t* target,
-                           const float* dice_coef, float w_ce, void* da, float* partials, float* dbias, float* dweight,
-                           double* loss_partials, int grid, void* stream);
+                           const float* dice_coef, float w_ce, void* da, void* dl8, float* partials, float* dbias,
+                           float* dweight, double* loss_partials, int grid, void* stream);
+int oct_head_apply_mfma(const OctHeadDesc* d, const void* dl8, const void* y, const float* scale, const float* shift,
+                        const float* w, const float* coef, void* dy, void* stream);
 #define HEAD_MAX_FEAT 128
 
 struct HeadParams {
@@ -513,6 +515,13 @@ extern "C" int oct_head_dlogits(const OctHeadDesc* d, const void* y, const float
   return oct_check_launch("head_dlogits");
 }
 
+// OCT_HEAD_MFMA=0 keeps the head backward on the vector kernel
+static bool head_mfma_on() {
+  static int on = -1;
+  if (on < 0) { const char* e = getenv("OCT_HEAD_MFMA"); on = (e && e[0] == '0') ? 0 : 1; }
+  return on != 0;
+}
+
 extern "C" int oct_head_backward_fused(const OctHeadDesc* d, const void* y, const float* scale, const float* shift,
                                        const float* mean, const float* invstd, const float* w, const float* b,
                                        const int64_t* target, const float* dice_coef, float w_ce, const float* dprobs,
@@ -530,14 +539,10 @@ extern "C" int oct_head_backward_fused(const OctHeadDesc* d, const void* y, cons
   OCT_CHECK(!dweight || d->classes <= 8, "oct_head_backward_fused: the fused weight gradient needs classes <= 8 (got %d)", d->classes);
   OCT_CHECK(dlogits || dweight, "oct_head_backward_fused: without dlogits the weight gradient must be fused (dweight)");
   OCT_CHECK(!loss_partials || target, "oct_head_backward_fused: loss partials need a target");
-  {
-    // matrix-pipe formulation (head_mfma.hip): bf16, loss from labels, fused dW, dlogits not requested
-    static int mfma_on = -1;
-    if (mfma_on < 0) { const char* e = getenv("OCT_HEAD_MFMA"); mfma_on = (e && e[0] == '0') ? 0 : 1; }
-    if (mfma_on && d->dtype == OCT_DT_BF16 && d->classes <= 8 && target && !dprobs && dweight && !dlogits)
-      return oct_head_backward_mfma(d, y, scale, shift, mean, invstd, w, b, target, dice_coef, w_ce, da, partials, dbias,
-                                    dweight, loss_partials, head_grid(d), stream);
-  }
+  // matrix-pipe formulation (head_mfma.hip): bf16, loss from labels, fused dW, dlogits not requested
+  if (head_mfma_on() && d->dtype == OCT_DT_BF16 && d->classes <= 8 && target && !dprobs && dweight && !dlogits)
+    return oct_head_backward_mfma(d, y, scale, shift, mean, invstd, w, b, target, dice_coef, w_ce, da, nullptr, partials, dbias,
+                                  dweight, loss_partials, head_grid(d), stream);
   const int grid = head_grid(d);
   hipStream_t s = as_stream(stream);
   const int cm = d->classes <= 2 ? 2 : d->classes <= 4 ? 4 : d->classes <= 8 ? 8 : 16;
@@ -553,4 +558,30 @@ extern "C" int oct_head_backward_fused(const OctHeadDesc* d, const void* y, cons
 #undef BYCLS
 #undef LAUNCH
   return oct_check_launch("head_bwd_fused");
+}
+
+// ---- the head hands dlogits, not dA, to the BatchNorm backward of the layer below (head_mfma.hip) -------------------
+// 1 exactly where oct_head_backward_fused runs the matrix-pipe kernel (given labels and a fused weight gradient)
+extern "C" int oct_head_backward_dl_ok(const OctHeadDesc* d) {
+  if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
+  if ((size_t)d->n * d->h * d->w > 0x7fffffffu) return 0;   // pixel indices are 32-bit in head_mfma.hip
+  return (head_mfma_on() && d->dtype == OCT_DT_BF16 && d->feat == 32 && d->classes > 0 && d->classes <= 8) ? 1 : 0;
+}
+
+extern "C" int oct_head_backward_dl(const OctHeadDesc* d, const void* y, const float* scale, const float* shift,
+                                    const float* mean, const float* invstd, const float* w, const float* b,
+                                    const int64_t* target, const float* dice_coef, float w_ce, void* dl8, float* partials,
+                                    float* dbias, float* dweight, double* loss_partials, void* stream) {
+  OCT_CHECK(oct_head_backward_dl_ok(d), "oct_head_backward_dl: not eligible (oct_head_backward_dl_ok): bf16, feat 32, classes <= 8");
+  OCT_CHECK(y && scale && shift && mean && invstd && w && b && target && dl8 && partials && dbias && dweight,
+            "oct_head_backward_dl: null pointer");
+  return oct_head_backward_mfma(d, y, scale, shift, mean, invstd, w, b, target, dice_coef, w_ce, nullptr, dl8, partials, dbias,
+                                dweight, loss_partials, head_grid(d), stream);
+}
+
+extern "C" int oct_head_bwd_apply(const OctHeadDesc* d, const void* dl8, const void* y, const float* scale, const float* shift,
+                                  const float* w, const float* coef, void* dy, void* stream) {
+  OCT_CHECK(oct_head_backward_dl_ok(d), "oct_head_bwd_apply: not eligible (oct_head_backward_dl_ok): bf16, feat 32, classes <= 8");
+  OCT_CHECK(dl8 && y && scale && shift && w && coef && dy, "oct_head_bwd_apply: null pointer");
+  return oct_head_apply_mfma(d, dl8, y, scale, shift, w, coef, dy, stream);
 }

@@ -29,11 +29,60 @@ struct HeadMfmaParams {
   const float* w; const float* b; const int64_t* target; const float* dice_coef;
   bf16_t* da; float* partials; float* dbias; float* dweight; double* loss_partials;
   float w_ce; int classes; unsigned npix;
+  bf16_t* dl8;   // DL8 form: [npix][8] bf16, the dA MFMA's B operand, written instead of da
 };
 
 __device__ __forceinline__ float hm_other(float v) { return __shfl_xor(v, 32); }            // lane r <-> lane r + 32
 __device__ __forceinline__ unsigned hm_other(unsigned v) { return (unsigned)__shfl_xor((int)v, 32); }
 
+// ---- dA = W^T . dl, defined once: the head kernel and the apply kernel below both call these, so a dA that is
+// recomputed from the stored dl fragment has the bits of the dA the head kernel summed ----------------------------
+// W^T as the A operand (rows = features, k = classes, zero beyond ncls), bf16 hi + lo
+__device__ __forceinline__ void hm_wt_frags(const float* __restrict__ w, int ncls, int r, int hh, bf16x8& wt_hi, bf16x8& wt_lo) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = 8 * hh + j;
+    const float v = c < ncls ? w[c * 32 + r] : 0.f;
+    const bf16_t h = (bf16_t)v;
+    wt_hi[j] = h;
+    wt_lo[j] = (bf16_t)(v - (float)h);
+  }
+}
+// dfr: dl as a B fragment (k = class): lanes hh = 0 carry the eight bf16 classes 0..7 of pixel r, lanes hh = 1 zeros.
+// dq: dA rounded to bf16, in the order of the loaded y fragments: dq[0..3] = features 8 hh .. 8 hh + 7, dq[4..7] = 16 + 8 hh ..
+__device__ __forceinline__ void hm_da(const bf16x8& wt_hi, const bf16x8& wt_lo, const u32x4 dfr, int hh, unsigned (&dq)[8]) {
+  typedef Mma<bf16_t> M;
+  const bf16x8 xd = __builtin_bit_cast(bf16x8, dfr);
+  f32x16 acd;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acd[i] = 0.f;
+  M::mma(acd, wt_hi, xd); M::mma(acd, wt_lo, xd);
+  // accumulator order: register i = feature (i & 3) + 8 (i >> 2) + 4 hh.  Packed, register pair g holds
+  // features 8 g + 4 hh .. + 3; the y order wants, for hh = 0: {0-3, 4-7 | 16-19, 20-23}, i.e. pairs
+  // g = 0 (own), g = 0 of the partner, g = 2 (own), g = 2 of the partner; for hh = 1: {8-11 (partner's
+  // g = 1), 12-15 (own g = 1) | 24-27 (partner's g = 3), 28-31 (own g = 3)}.
+  unsigned cpk[8];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    cpk[2 * g] = pack_bf16x2(acd[4 * g], acd[4 * g + 1]);
+    cpk[2 * g + 1] = pack_bf16x2(acd[4 * g + 2], acd[4 * g + 3]);
+  }
+  // each lane sends the two pairs its partner needs: hh = 0 sends g = 1, 3; hh = 1 sends g = 0, 2
+  const unsigned sA0 = hh ? cpk[0] : cpk[2], sA1 = hh ? cpk[1] : cpk[3];
+  const unsigned sB0 = hh ? cpk[4] : cpk[6], sB1 = hh ? cpk[5] : cpk[7];
+  const unsigned rA0 = hm_other(sA0), rA1 = hm_other(sA1), rB0 = hm_other(sB0), rB1 = hm_other(sB1);
+  if (hh == 0) {
+    dq[0] = cpk[0]; dq[1] = cpk[1]; dq[2] = rA0; dq[3] = rA1;
+    dq[4] = cpk[4]; dq[5] = cpk[5]; dq[6] = rB0; dq[7] = rB1;
+  } else {
+    dq[0] = rA0; dq[1] = rA1; dq[2] = cpk[2]; dq[3] = cpk[3];
+    dq[4] = rB0; dq[5] = rB1; dq[6] = cpk[6]; dq[7] = cpk[7];
+  }
+}
+
+// DL8 = false: dA goes out as the NHWC tensor [npix][32].  DL8 = true: the 16-B dl fragment goes out instead and
+// head_bwd_apply_kernel recomputes dA from it (48 B per pixel less written here, 48 B less read there).
+template <bool DL8>
 __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const HeadMfmaParams p) {
   typedef Mma<bf16_t> M;
   typedef M::Frag Frag;
@@ -64,14 +113,7 @@ __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const Head
       wl_lo[s][j] = (bf16_t)(v - (float)h);
     }
   Frag wt_hi, wt_lo;         // dA: rows = features, k = classes (zero beyond)
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = 8 * hh + j;
-    const float v = c < ncls ? p.w[c * F + r] : 0.f;
-    const bf16_t h = (bf16_t)v;
-    wt_hi[j] = h;
-    wt_lo[j] = (bf16_t)(v - (float)h);
-  }
+  hm_wt_frags(p.w, ncls, r, hh, wt_hi, wt_lo);
   // this lane's 16 features in the order of the loaded fragments: f(q, j) = 16 q + 8 hh + j
   float sc[16], sh[16];
 #pragma unroll
@@ -190,34 +232,11 @@ __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const Head
     // dl as a B fragment (k = class): lanes hh = 0 carry classes 0..7 (their own four + the partner's), hh = 1 zeros
     const unsigned o0 = hm_other(dpk[0]), o1 = hm_other(dpk[1]);
     const u32x4 dfr = {hh ? 0u : dpk[0], hh ? 0u : dpk[1], hh ? 0u : o0, hh ? 0u : o1};
-    const Frag xd = __builtin_bit_cast(Frag, dfr);
-    f32x16 acd;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acd[i] = 0.f;
-    M::mma(acd, wt_hi, xd); M::mma(acd, wt_lo, xd);
-    // accumulator order: register i = feature (i & 3) + 8 (i >> 2) + 4 hh.  Packed, register pair g holds
-    // features 8 g + 4 hh .. + 3; the y order wants, for hh = 0: {0-3, 4-7 | 16-19, 20-23}, i.e. pairs
-    // g = 0 (own), g = 0 of the partner, g = 2 (own), g = 2 of the partner; for hh = 1: {8-11 (partner's
-    // g = 1), 12-15 (own g = 1) | 24-27 (partner's g = 3), 28-31 (own g = 3)}.
-    unsigned cpk[8];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      cpk[2 * g] = pack_bf16x2(acd[4 * g], acd[4 * g + 1]);
-      cpk[2 * g + 1] = pack_bf16x2(acd[4 * g + 2], acd[4 * g + 3]);
-    }
-    // each lane sends the two pairs its partner needs: hh = 0 sends g = 1, 3; hh = 1 sends g = 0, 2
-    const unsigned sA0 = hh ? cpk[0] : cpk[2], sA1 = hh ? cpk[1] : cpk[3];
-    const unsigned sB0 = hh ? cpk[4] : cpk[6], sB1 = hh ? cpk[5] : cpk[7];
-    const unsigned rA0 = hm_other(sA0), rA1 = hm_other(sA1), rB0 = hm_other(sB0), rB1 = hm_other(sB1);
     unsigned dq[8];          // dA in the y order: dq[0..3] = features 8 hh .. 8 hh + 7, dq[4..7] = 16 + 8 hh ..
-    if (hh == 0) {
-      dq[0] = cpk[0]; dq[1] = cpk[1]; dq[2] = rA0; dq[3] = rA1;
-      dq[4] = cpk[4]; dq[5] = cpk[5]; dq[6] = rB0; dq[7] = rB1;
-    } else {
-      dq[0] = rA0; dq[1] = rA1; dq[2] = cpk[2]; dq[3] = cpk[3];
-      dq[4] = rB0; dq[5] = rB1; dq[6] = cpk[6]; dq[7] = cpk[7];
-    }
-    if (valid) {
+    hm_da(wt_hi, wt_lo, dfr, hh, dq);
+    if (DL8) {
+      if (valid && hh == 0) *reinterpret_cast<u32x4*>(p.dl8 + (size_t)pix * 8) = dfr;
+    } else if (valid) {
       const u32x4 o0v = {dq[0], dq[1], dq[2], dq[3]}, o1v = {dq[4], dq[5], dq[6], dq[7]};
       *reinterpret_cast<u32x4*>(p.da + (size_t)pix * F + 8 * hh) = o0v;
       *reinterpret_cast<u32x4*>(p.da + (size_t)pix * F + 16 + 8 * hh) = o1v;
@@ -287,16 +306,99 @@ __global__ void __launch_bounds__(HM_THREADS, 2) head_bwd_mfma_kernel(const Head
   }
 }
 
-// launched by oct_head_backward_fused (head.hip) when eligible; `grid` = oct_head_blocks
+// dy = k0 * ([y*scale + shift > 0] ? dA : 0) + k1 * y + k2 with dA = bf16(W^T . dl) recomputed from the 16-B dl fragment the
+// DL8 head kernel stored: bn_bwd_apply_flat_kernel's arithmetic (bn.hip), fma for fma, on hm_da's bits -- the pass reads
+// 16 + 64 B per pixel instead of 64 + 64.  One wave per 32 pixels and iteration in the head kernel's lane mapping, the next
+// group's rows in flight.
+struct HeadApplyParams {
+  const bf16_t* dl8; const bf16_t* y; const float* scale; const float* shift; const float* w; const float* coef;
+  bf16_t* dy; int classes; unsigned npix;
+};
+
+__global__ void __launch_bounds__(HM_THREADS) head_bwd_apply_kernel(const HeadApplyParams p) {
+  typedef unsigned int nt_u4 __attribute__((ext_vector_type(4)));
+  constexpr int F = 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  bf16x8 wt_hi, wt_lo;
+  hm_wt_frags(p.w, p.classes, r, hh, wt_hi, wt_lo);
+  // this lane's 16 features in the order of the loaded fragments: f(q, j) = 16 q + 8 hh + j
+  float sc[16], sh[16], k0[16], k1[16], k2[16];
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int f = 16 * q + 8 * hh + j;
+      sc[8 * q + j] = p.scale[f]; sh[8 * q + j] = p.shift[f];
+      k0[8 * q + j] = p.coef[f]; k1[8 * q + j] = p.coef[F + f]; k2[8 * q + j] = p.coef[2 * F + f];
+    }
+  const unsigned ngroups = (p.npix + 31) / 32;
+  const unsigned gstride = gridDim.x * (HM_THREADS / 64);
+  unsigned grp = blockIdx.x * (HM_THREADS / 64) + wave;
+  // the rows of pixel min(32 g + r, npix - 1): the tail group re-reads the last pixel and stores nothing for it
+  auto load = [&](unsigned g, nt_u4& y0, nt_u4& y1, nt_u4& dn) {
+    const unsigned px = min(g * 32 + r, p.npix - 1);
+    y0 = __builtin_nontemporal_load(reinterpret_cast<const nt_u4*>(p.y + (size_t)px * F + 8 * hh));
+    y1 = __builtin_nontemporal_load(reinterpret_cast<const nt_u4*>(p.y + (size_t)px * F + 16 + 8 * hh));
+    if (hh == 0) dn = __builtin_nontemporal_load(reinterpret_cast<const nt_u4*>(p.dl8 + (size_t)px * 8));
+  };
+  nt_u4 yn0, yn1, dn = {0u, 0u, 0u, 0u};   // lanes hh = 1 never load dl: their half of the B fragment is zero
+  if (grp < ngroups) load(grp, yn0, yn1, dn);
+  for (; grp < ngroups; grp += gstride) {
+    const unsigned pix = grp * 32 + r;
+    const nt_u4 y0 = yn0, y1 = yn1;
+    const u32x4 dfr = {dn[0], dn[1], dn[2], dn[3]};
+    if (grp + gstride < ngroups) load(grp + gstride, yn0, yn1, dn);
+    unsigned dq[8];
+    hm_da(wt_hi, wt_lo, dfr, hh, dq);
+    unsigned o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const unsigned yw = j < 4 ? y0[j] : y1[j - 4];
+      const float ya = bf16lo(yw), yb = bf16hi(yw);
+      const float ga = fmaf(ya, sc[2 * j], sh[2 * j]) > 0.f ? bf16lo(dq[j]) : 0.f;
+      const float gb = fmaf(yb, sc[2 * j + 1], sh[2 * j + 1]) > 0.f ? bf16hi(dq[j]) : 0.f;
+      o[j] = pack_bf16x2(fmaf(k0[2 * j], ga, fmaf(k1[2 * j], ya, k2[2 * j])),
+                         fmaf(k0[2 * j + 1], gb, fmaf(k1[2 * j + 1], yb, k2[2 * j + 1])));
+    }
+    if (pix < p.npix) {
+      const nt_u4 o0v = {o[0], o[1], o[2], o[3]}, o1v = {o[4], o[5], o[6], o[7]};
+      __builtin_nontemporal_store(o0v, reinterpret_cast<nt_u4*>(p.dy + (size_t)pix * F + 8 * hh));
+      __builtin_nontemporal_store(o1v, reinterpret_cast<nt_u4*>(p.dy + (size_t)pix * F + 16 + 8 * hh));
+    }
+  }
+}
+
+// Grid cap of the apply pass: bn.hip's EW_MAX_BLOCKS argument (about 4 MB of loads in flight chip-wide).  A wave has one
+// group of 32 pixels x 80 B = 2.5 KB in flight, a workgroup 10 KB: 512 workgroups = 5 MB.  Measured at 32 x 512 x 1024:
+// 256 / 384 / 512 / 768 / 1024 / 2048 / 4096 workgroups -> 0.52 / 0.57 / 0.50 / 0.51 / 0.54 / 0.52 / 0.51 ms.
+#define HM_APPLY_MAX_BLOCKS 512
+
+// launched by oct_head_backward_fused / oct_head_backward_dl (head.hip) when eligible; `grid` = oct_head_blocks.
+// dl8 != NULL: the DL8 form (da is not written)
 int oct_head_backward_mfma(const OctHeadDesc* d, const void* y, const float* scale, const float* shift, const float* mean,
                            const float* invstd, const float* w, const float* b, const int64_t* target,
-                           const float* dice_coef, float w_ce, void* da, float* partials, float* dbias, float* dweight,
-                           double* loss_partials, int grid, void* stream) {
+                           const float* dice_coef, float w_ce, void* da, void* dl8, float* partials, float* dbias,
+                           float* dweight, double* loss_partials, int grid, void* stream) {
   HeadMfmaParams p;
   p.y = (const bf16_t*)y; p.scale = scale; p.shift = shift; p.mean = mean; p.invstd = invstd; p.w = w; p.b = b;
-  p.target = target; p.dice_coef = dice_coef; p.da = (bf16_t*)da; p.partials = partials; p.dbias = dbias;
+  p.target = target; p.dice_coef = dice_coef; p.da = (bf16_t*)da; p.dl8 = (bf16_t*)dl8; p.partials = partials; p.dbias = dbias;
   p.dweight = dweight; p.loss_partials = loss_partials; p.w_ce = w_ce; p.classes = d->classes;
   p.npix = (unsigned)((size_t)d->n * d->h * d->w);
-  hipLaunchKernelGGL(head_bwd_mfma_kernel, dim3(grid), dim3(HM_THREADS), 0, as_stream(stream), p);
+  if (dl8) hipLaunchKernelGGL(head_bwd_mfma_kernel<true>, dim3(grid), dim3(HM_THREADS), 0, as_stream(stream), p);
+  else hipLaunchKernelGGL(head_bwd_mfma_kernel<false>, dim3(grid), dim3(HM_THREADS), 0, as_stream(stream), p);
   return oct_check_launch("head_bwd_mfma");
+}
+
+int oct_head_apply_mfma(const OctHeadDesc* d, const void* dl8, const void* y, const float* scale, const float* shift,
+                        const float* w, const float* coef, void* dy, void* stream) {
+  HeadApplyParams p;
+  p.dl8 = (const bf16_t*)dl8; p.y = (const bf16_t*)y; p.scale = scale; p.shift = shift; p.w = w; p.coef = coef;
+  p.dy = (bf16_t*)dy; p.classes = d->classes;
+  p.npix = (unsigned)((size_t)d->n * d->h * d->w);
+  const unsigned ngroups = (p.npix + 31) / 32, per = HM_THREADS / 64;
+  unsigned grid = (ngroups + per - 1) / per;
+  if (grid > HM_APPLY_MAX_BLOCKS) grid = HM_APPLY_MAX_BLOCKS;
+  hipLaunchKernelGGL(head_bwd_apply_kernel, dim3(grid), dim3(HM_THREADS), 0, as_stream(stream), p);
+  return oct_check_launch("head_bwd_apply");
 }

@@ -15,6 +15,8 @@
 //    across the whole persistent tile loop and issues its fp32 atomics once at the end.
 #include "common.h"
 
+#include <type_traits>
+
 struct Wgrad2Params {
   const bf16_t* x0; const bf16_t* x1;
   const float* sc0; const float* sh0; const float* sc1; const float* sh1;
@@ -32,6 +34,9 @@ struct Wgrad2Params {
   // (y0 - pad_y, x0 - 1); only the first `nstore` of the nine accumulators are real taps (the last launch has one tap row)
   int ty0, pad_y, nstore;
   unsigned long long* trace;   // diagnostic builds only (-DOCT_TRACE): s_memtime stamps of workgroup (0,0,0)
+  // DYAPPLY: `dy` holds dA; the producers form dY = k0 * [y*scale + shift > 0] * dA + k1 * y + k2 on load (coef = [3][cout]),
+  // commit it to the LDS tile and store it to dy_out (which may be `dy` itself)
+  const bf16_t* dy_y; const float* dy_coef; const float* dy_sc; const float* dy_sh; bf16_t* dy_out;
 };
 
 #ifdef OCT_TRACE
@@ -52,15 +57,26 @@ static constexpr int w2_inb(int taps, int th) { return (th + 2 * (taps == 9 ? 1 
 static constexpr int w2_dyb(int th) { return th * 32 * 64; }                                                                     // dY tile of a 32-channel block
 static constexpr int w2_stage(int taps, int cb, int ib, int th) { return ib * w2_inb(taps, th) + cb * w2_dyb(th); }   // a stage: [ib] input tiles, [cb] dY tiles
 static constexpr int w2_sxf(int taps, int cb, int ib, int th) { return 2 * w2_stage(taps, cb, ib, th); }              // after the two stages: float [2][32 * ib]
-static constexpr int w2_lds(int taps, int cb, int ib, int th) { return w2_sxf(taps, cb, ib, th) + 2 * 32 * ib * (int)sizeof(float); }
+static constexpr int w2_sdy(int taps, int cb, int ib, int th) { return w2_sxf(taps, cb, ib, th) + 2 * 32 * ib * (int)sizeof(float); }   // DYAPPLY: float [5][32 * cb]
+static constexpr int w2_lds(int taps, int cb, int ib, int th, bool dyapply = false) {
+  return w2_sdy(taps, cb, ib, th) + (dyapply ? 5 * 32 * cb * (int)sizeof(float) : 0);
+}
 
 // D3: depth shift of the input tile / image map of an S2D dY (volumetric network) -- compile-time, see igemm2.hip
 // RSH: the nine taps are rows ty0 .. ty0 + 2 of a TALLER kernel (ReLayNet's 7x3, ReLayNet_2017.py:155-160, padding (3, 1)):
 // dW[ty0 + ty][tx] = sum dY[y][x] * A[y - pad_y + ty0 + ty][x - 1 + tx].  Same tile, same loop; the input tile is fetched
 // ty0 - pad_y + 1 rows further down and its rows are checked against the image by range instead of by halo flags (a shifted
 // tile reaches padding on more tile rows than the first and the last).
-template <int TAPS, int CB, int IB, int TH, bool RAGGED, bool D3 = false, bool RSH = false>
+// DYAPPLY: the BatchNorm backward of the layer is applied by the producers when they stage dY, and dY is stored for the data
+// gradient (Wgrad2Params.dy_y ...).  Only for a single-column grid (gridDim.y == gridDim.z == 1): every 16-B chunk of dY is
+// then staged by exactly one producer thread of one workgroup, which reads its dA chunk before it stores the dY chunk -- so
+// dy_out may be the dA tensor itself.  Whole tiles, plain dY (wgrad2_apply_store_ok).
+struct W2NoY {};
+template <int CB, int SDB> struct W2StageY { u32x4 ry[CB][SDB]; const unsigned char* ob; };   // y chunks of the dY slots; dy_out of the tile
+
+template <int TAPS, int CB, int IB, int TH, bool RAGGED, bool D3 = false, bool RSH = false, bool DYAPPLY = false>
 __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
+  static_assert(!DYAPPLY || (TAPS == 9 && !RAGGED && !D3 && !RSH), "DYAPPLY: plain 3x3, whole tiles");
   constexpr int TW = 32;
   // TAPS = 9: 3x3; TAPS = 3: one row of three (the seventh row of ReLayNet's 7x3, always row-shifted: RSH); TAPS = 1: 1x1
   constexpr int HALO = (TAPS != 1) ? 1 : 0;        // columns
@@ -71,8 +87,9 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
   constexpr int INB = w2_inb(TAPS, TH), DYB = w2_dyb(TH);        // bytes per 32-channel block
   constexpr int STAGEB = w2_stage(TAPS, CB, IB, TH);
   static_assert(INB == NPI * 64 && DYB == NPD * 64, "the layout's tiles are the kernel's");
-  static_assert(w2_sxf(TAPS, CB, IB, TH) % 16 == 0 && w2_lds(TAPS, CB, IB, TH) % 16 == 0, "every region stays 16-B aligned");
-  static_assert(w2_lds(TAPS, CB, IB, TH) <= OCT_LDS_CAP, "LDS budget");
+  static_assert(w2_sxf(TAPS, CB, IB, TH) % 16 == 0 && w2_sdy(TAPS, CB, IB, TH) % 16 == 0 && w2_lds(TAPS, CB, IB, TH, DYAPPLY) % 16 == 0,
+                "every region stays 16-B aligned");
+  static_assert(w2_lds(TAPS, CB, IB, TH, DYAPPLY) <= OCT_LDS_CAP, "LDS budget");
   // W16 (3x3 kernels): v_mfma_f32_16x16x32_bf16 -- a fragment is 32 pixels (a whole tile row) x 16 channels, D = 16 co x 16 ci
   // in quarter S = 2*(co half) + (ci half) of the tap's accumulator: register 4S + e = (co 16a + 4*(lane>>4) + e, ci 16b + (lane&15)).
   // Same FLOPs, LDS reads and loop as the 32x32x16 form (pixel halves become channel halves); the chip holds a higher clock
@@ -122,6 +139,15 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
     sxf[i] = xf ? (second ? p.sc1[cg - p.c0] : p.sc0[cg]) : 1.f;
     sxf[32 * IB + i] = xf ? (second ? p.sh1[cg - p.c0] : p.sh0[cg]) : 0.f;
   }
+  // DYAPPLY: k0, k1, k2, scale, shift of this workgroup's output channels: [5][32 * CB]
+  float* const sdy = reinterpret_cast<float*>(smem + w2_sdy(TAPS, CB, IB, TH));
+  if constexpr (DYAPPLY) {
+    for (int i = tid; i < 32 * CB; i += 512) {
+      const int ch = co_sb + i;
+      sdy[i] = p.dy_coef[ch]; sdy[32 * CB + i] = p.dy_coef[p.cout + ch]; sdy[2 * 32 * CB + i] = p.dy_coef[2 * p.cout + ch];
+      sdy[3 * 32 * CB + i] = p.dy_sc[ch]; sdy[4 * 32 * CB + i] = p.dy_sh[ch];
+    }
+  }
   __syncthreads();
 
   if (wave >= 4) {
@@ -132,7 +158,8 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
     constexpr int D = DRING;
     // (img, tyi, txi: written by issue(), read by nothing since the LDS-DMA staging of dY was removed; without them hipcc
     //  numbers the registers of the depth-tap instantiation differently, so they stay until the loop is next touched)
-    struct Stage { u32x4 ri[IB][SIB]; u32x4 rd[CB][SDB]; unsigned vm[IB]; unsigned vd; int img, tyi, txi; };
+    typedef typename std::conditional<DYAPPLY, W2StageY<CB, SDB>, W2NoY>::type StageY;
+    struct Stage { u32x4 ri[IB][SIB]; u32x4 rd[CB][SDB]; unsigned vm[IB]; unsigned vd; int img, tyi, txi; StageY yy; };
     Stage R[D];
     // per-slot constants (shared by all blocks): pixel offset from the tile origin + border code
     int reli[SIB], reld[SDB];
@@ -234,9 +261,17 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
           vd |= ok ? (1u << j) : 0u;
         }
         if (RAGGED) S.vd = vd;
+        if constexpr (DYAPPLY) {   // the y chunk of every dY slot: same tensor shape, same offsets (plain dY, whole tiles)
+          const unsigned char* const yb = reinterpret_cast<const unsigned char*>(p.dy_y + origin * cs + row);
+#pragma unroll
+          for (int j = 0; j < SDB; ++j)
+            S.yy.ry[blk][j] = *reinterpret_cast<const u32x4*>(yb + (__umul24((unsigned)reld[j], cs2) + (unsigned)g * 16u));
+          if (blk == 0) S.yy.ob = reinterpret_cast<const unsigned char*>(p.dy_out + origin * cs + co_sb);
+        }
       }
     };
-    auto commit = [&](unsigned char* buf, const Stage& S) {
+    // st (DYAPPLY): the stage is a real one, its dY goes to dy_out
+    auto commit = [&](unsigned char* buf, const Stage& S, const bool st) {
 #pragma unroll
       for (int blk = 0; blk < IB; ++blk) {
         const int cg = ci_sb + blk * 32;
@@ -272,10 +307,38 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
         }
       }
 #pragma unroll
-      for (int blk = 0; blk < CB; ++blk)
+      for (int blk = 0; blk < CB; ++blk) {
+        // DYAPPLY: this thread's eight channels never change: dY = fmaf(k0, [fmaf(y, sc, sh) > 0] ? dA : 0, fmaf(k1, y, k2)),
+        // bn_bwd_apply_flat_kernel's arithmetic (bn.hip), rounded to bf16 once -- the value the LDS tile and dy_out both get
+        float k0[8], k1[8], k2[8], ysc[8], ysh[8];
+        if constexpr (DYAPPLY) {
+          const float* const t = sdy + blk * 32 + g * 8;
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(t + 4 * q), a1 = *reinterpret_cast<const f32x4*>(t + 32 * CB + 4 * q);
+            const f32x4 a2 = *reinterpret_cast<const f32x4*>(t + 2 * 32 * CB + 4 * q), a3 = *reinterpret_cast<const f32x4*>(t + 3 * 32 * CB + 4 * q);
+            const f32x4 a4 = *reinterpret_cast<const f32x4*>(t + 4 * 32 * CB + 4 * q);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { k0[4 * q + e] = a0[e]; k1[4 * q + e] = a1[e]; k2[4 * q + e] = a2[e]; ysc[4 * q + e] = a3[e]; ysh[4 * q + e] = a4[e]; }
+          }
+        }
 #pragma unroll
         for (int j = 0; j < SDB; ++j) {
           u32x4 v = S.rd[blk][j];
+          if constexpr (DYAPPLY) {
+            const u32x4 yv = S.yy.ry[blk][j];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float ya = bf16lo(yv[e]), yb = bf16hi(yv[e]);
+              const float ga = fmaf(ya, ysc[2 * e], ysh[2 * e]) > 0.f ? bf16lo(v[e]) : 0.f;
+              const float gb = fmaf(yb, ysc[2 * e + 1], ysh[2 * e + 1]) > 0.f ? bf16hi(v[e]) : 0.f;
+              v[e] = pack_bf16x2(fmaf(k0[2 * e], ga, fmaf(k1[2 * e], ya, k2[2 * e])),
+                                 fmaf(k0[2 * e + 1], gb, fmaf(k1[2 * e + 1], yb, k2[2 * e + 1])));
+            }
+            // the padded stages behind the last tile re-stage it (and, with dy_out == dy, re-read what this thread stored): no store
+            if (st) *reinterpret_cast<u32x4*>(const_cast<unsigned char*>(S.yy.ob) + (size_t)blk * 64 +
+                                              (__umul24((unsigned)reld[j], 2u * (unsigned)p.cout) + (unsigned)g * 16u)) = v;
+          }
           if (RAGGED) {
             const bool live = ((S.vd >> j) & 1u) != 0;   // dY rows / columns of a ragged tile beyond the image: zero
 #pragma unroll
@@ -283,11 +346,12 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
           }
           *reinterpret_cast<u32x4*>(buf + IB * INB + blk * DYB + (pb + 64 * j) * 64 + ((unsigned)g ^ dswz[j]) * 16) = v;
         }
+      }
     };
     const int last = nstage - 1;
 #pragma unroll
     for (int j = 0; j < D; ++j) issue(min(j, last), R[j]);
-    commit(stage0, R[0]);
+    commit(stage0, R[0], true);
     issue(min(D, last), R[0]);
     __syncthreads();
     // branch-free steady state over the padded stage count (see igemm2.hip)
@@ -296,7 +360,7 @@ __global__ void __launch_bounds__(512) wgrad2_kernel(const Wgrad2Params p) {
       for (int j = 0; j < D; ++j) {
         const int nx = s0 + j + 1;
         if (wave == 4) W2TRACE(4, nx - 1);
-        commit(stage0 + (nx & 1) * STAGEB, R[(j + 1) % D]);
+        commit(stage0 + (nx & 1) * STAGEB, R[(j + 1) % D], nx <= last);
         if (wave == 4) W2TRACE(5, nx - 1);
         issue(min(nx + D, last), R[(j + 1) % D]);
         if (wave == 4) W2TRACE(6, nx - 1);
@@ -543,14 +607,14 @@ static W2Grid w2_grid(int taps, int cb, int ib, int th, int nco, int nci, int n,
   return g;
 }
 
-template <int TAPS, int CB, int IB, int TH, bool RAGGED, bool D3 = false, bool RSH = false>
+template <int TAPS, int CB, int IB, int TH, bool RAGGED, bool D3 = false, bool RSH = false, bool DYAPPLY = false>
 static int launch_w2r(Wgrad2Params& p, int nco, int nci, hipStream_t s) {
-  constexpr int lds = w2_lds(TAPS, CB, IB, TH);
-  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&wgrad2_kernel<TAPS, CB, IB, TH, RAGGED, D3, RSH>), lds)) return rc;
+  constexpr int lds = w2_lds(TAPS, CB, IB, TH, DYAPPLY);
+  if (const int rc = oct_lds_optin(reinterpret_cast<const void*>(&wgrad2_kernel<TAPS, CB, IB, TH, RAGGED, D3, RSH, DYAPPLY>), lds)) return rc;
   const W2Grid g = w2_grid(TAPS, CB, IB, TH, nco, nci, p.n, p.h, p.w);
   p.tiles_x = (p.w + 31) / 32; p.tiles_y = (p.h + TH - 1) / TH; p.ntiles = p.tiles_x * p.tiles_y * p.n;
   p.per_wg = g.per_wg; p.interleave = g.interleave;
-  hipLaunchKernelGGL((wgrad2_kernel<TAPS, CB, IB, TH, RAGGED, D3, RSH>), dim3(g.gx, nco / CB, nci / IB), dim3(512), lds, s, p);
+  hipLaunchKernelGGL((wgrad2_kernel<TAPS, CB, IB, TH, RAGGED, D3, RSH, DYAPPLY>), dim3(g.gx, nco / CB, nci / IB), dim3(512), lds, s, p);
   return OCT_OK;
 }
 template <int TAPS, int CB, int IB, int TH>
@@ -607,9 +671,22 @@ bool wgrad2_plan(const OctWgradDesc* d, WgradPlan* pl) {
   return true;
 }
 
+// Where the launch can apply the BatchNorm backward on load and store dY (OctWgradArgs.dy_coef + dy_out, DYAPPLY): plain 3x3 in
+// atomics mode over whole tiles, a single-column grid (each dY chunk has one producer thread: the kernel's comment), and the
+// channel-block shape that is instantiated -- 32 x 64 (Cout = 32, Cin = 64: the first convolution of the last decoder block).
+bool wgrad2_apply_store_ok(const OctWgradDesc* d, const WgradPlan& pl) {
+  if (pl.path != WGRAD_W2 || d->taps != 9 || d->kh == 7 || d->depth > 0 || d->dy_img_mul != 0 || d->dy_mode != OCT_IN_PLAIN || d->partials)
+    return false;
+  if ((d->w % 32) != 0 || (d->h % pl.th) != 0) return false;
+  const int nco = d->cout / 32, nci = (d->c0 + d->c1) / 32;
+  if (nco / pl.cb != 1 || nci / pl.ib != 1) return false;
+  return pl.cb == 1 && pl.ib == 2 && pl.th == 8;
+}
+
 int launch_wgrad2(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs* a, hipStream_t s) {
   const int ktot = d->c0 + d->c1;
   Wgrad2Params p;
+  p.dy_y = (const bf16_t*)a->dy_y; p.dy_coef = a->dy_coef; p.dy_sc = a->dy_scale; p.dy_sh = a->dy_shift; p.dy_out = (bf16_t*)a->dy_out;
   p.x0 = (const bf16_t*)a->x0; p.x1 = (const bf16_t*)a->x1;
   p.sc0 = a->scale0; p.sh0 = a->shift0; p.sc1 = a->scale1; p.sh1 = a->shift1;
   p.dy = (const bf16_t*)a->dy; p.dwp = a->dwp; p.dbias = a->dbias;
@@ -639,6 +716,8 @@ int launch_wgrad2(const WgradPlan& pl, const OctWgradDesc* d, const OctWgradArgs
       if (ty0 == 6) rc = whole ? launch_w2r<3, 2, 2, 8, false, false, true>(p, nco, nci, s) : launch_w2r<3, 2, 2, 8, true, false, true>(p, nco, nci, s);
       else rc = whole ? launch_w2r<9, 2, 2, 8, false, false, true>(p, nco, nci, s) : launch_w2r<9, 2, 2, 8, true, false, true>(p, nco, nci, s);
     }
+  } else if (a->dy_coef) {   // apply + store (the dispatcher admitted it: wgrad2_apply_store_ok)
+    rc = launch_w2r<9, 1, 2, 8, false, false, false, true>(p, nco, nci, s);
   } else if (d->taps == 9) {
     if (pl.cb == 2 && pl.ib == 2) rc = launch_w2<9, 2, 2, 8>(p, nco, nci, s);
     else if (pl.ib == 2) rc = launch_w2<9, 1, 2, 8>(p, nco, nci, s);

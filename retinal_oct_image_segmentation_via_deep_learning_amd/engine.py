@@ -175,6 +175,8 @@ class UNetEngine:
         # summed in order) instead of fp32 atomics -- bit-identical gradients from run to run (OCT_DETERMINISTIC=1 sets it)
         self.deterministic = os.environ.get("OCT_DETERMINISTIC", "0") == "1"
         self.fused_bwd_off = False   # True: the 32 -> 32 layers keep the separate dW / dX / BatchNorm-reduction launches (parity tests)
+        self.head_dl_off = False     # True: the head writes dA and the last block's BatchNorm backward reads it back (parity tests)
+        self.wgrad_apply_off = False   # True: dec1.conv1 keeps the separate oct_bn_bwd_apply launch in front of its weight gradient (parity tests)
         self.debug = None  # set to a dict to capture intermediate gradients (tests / probes)
         self.prof = None   # set to a list: (kind, start_event, end_event) around every MFMA launch
         self.prof_labels = None   # set to a list next to `prof`: (taps, cin, cout, n, h, w, in/dy mode, out mode) per launch
@@ -280,8 +282,9 @@ class UNetEngine:
         return L.lib().oct_conv_stat_blocks(C.byref(d))
 
     def _wgrad(self, src: Src, dy, cout, taps, n, h, w, dy_mode=L.IN_PLAIN, dbias=None, fused_apply=None, kh=0, kw=0,
-               depth=0, in_shift=0, dy_img=(0, 0), dwp=None, partials_ok=True):
-        """fused_apply = (y, coef, scale, shift): `dy` holds dA and the kernel applies BN backward on load.
+               depth=0, in_shift=0, dy_img=(0, 0), dwp=None, partials_ok=True, dy_out=None):
+        """fused_apply = (y, coef, scale, shift): `dy` holds dA and the kernel applies BN backward on load; with dy_out it
+        also stores the dY it forms there (dy_out may be `dy`; oct_conv_wgrad_apply_store_ok).
         depth / in_shift / dy_img: one depth tap of a 3-D weight gradient (oct_hip.h, OctWgradDesc); dwp: write into this
         (zeroed) slab instead of taking a new one.  partials_ok: the caller unpacks through `_unpack` (OctUnpackJob.nparts
         sums the per-workgroup slabs of deterministic mode); callers of the single-slab unpack entry points
@@ -304,7 +307,7 @@ class UNetEngine:
                         L.ptr(src.bn0.scale) if src.bn0 else None, L.ptr(src.bn0.shift) if src.bn0 else None,
                         L.ptr(src.bn1.scale) if src.bn1 else None, L.ptr(src.bn1.shift) if src.bn1 else None,
                         L.ptr(dy), L.ptr(dwp), L.ptr(dbias), *([L.ptr(t) for t in fused_apply] if fused_apply
-                                                                 else [None, None, None, None]), L.ptr(bias_parts))
+                                                                 else [None, None, None, None]), L.ptr(bias_parts), L.ptr(dy_out))
         ev = self._prof_begin()
         L.check(L.lib().oct_conv_wgrad(C.byref(d), C.byref(a), _stream()), "oct_conv_wgrad")
         self._prof_end(ev, "wgrad", (taps, ktot, cout, n, h, w, dy_mode, 0))
@@ -493,9 +496,11 @@ class UNetEngine:
         return ctx, probs, amax, logits
 
     # ---- backward -------------------------------------------------------------------------------
-    def _bn_backward(self, rec: ConvRec, da, dpool, G, accumulate, partials=None, defer_apply=False):
+    def _bn_backward(self, rec: ConvRec, da, dpool, G, accumulate, partials=None, defer_apply=False, head_dl=None):
         """da (and/or pooled gradient) wrt relu(bn(y)) -> dy in place; BN parameter grads.
-        partials: reduction already done by the producer of da (fused head backward)."""
+        partials: reduction already done by the producer of da (fused head backward).
+        head_dl = (head descriptor, dl8, head weight): da is None, the head stored d(loss)/d(logits) instead and the
+        apply pass recomputes dA = W^T dl from it (oct_head_bwd_apply); comes with partials."""
         lib = L.lib()
         n, h, w, c = rec.n, rec.h, rec.w, rec.cout
         dev = rec.y.device
@@ -535,6 +540,12 @@ class UNetEngine:
                                               rec.bn.shift.data_ptr(), coef.data_ptr(), g.data_ptr(), n, h, w, c, _stream()),
                     "oct_bn_bwd_apply_pool")
             return g
+        if head_dl is not None:
+            hd, dl8, hw = head_dl
+            L.check(lib.oct_head_bwd_apply(C.byref(hd), dl8.data_ptr(), rec.y.data_ptr(), rec.bn.scale.data_ptr(),
+                                           rec.bn.shift.data_ptr(), hw.data_ptr(), coef.data_ptr(), g.data_ptr(), _stream()),
+                    "oct_head_bwd_apply")
+            return g
         L.check(lib.oct_bn_bwd_apply(self.dt, g.data_ptr(), rec.y.data_ptr(), coef.data_ptr(),
                                      None if pooled else rec.bn.scale.data_ptr(),
                                      None if pooled else rec.bn.shift.data_ptr(), n * h * w, c, _stream()),
@@ -545,12 +556,27 @@ class UNetEngine:
             self.debug["coef:" + rec.wkey] = coef.clone()
         return g
 
-    def _conv_backward(self, rec: ConvRec, dy, G, accumulate, need_dx=True):
-        """dW of the conv (into G) and, if needed, the gradient(s) wrt its (virtually concatenated) input."""
+    def _wgrad_applies(self, rec: ConvRec) -> bool:
+        """The weight gradient of this convolution can apply the BatchNorm backward of its output on load and store dY for the
+        data gradient (no oct_bn_bwd_apply launch).  The library decides; the debug path records dY from the separate launch
+        and deterministic mode runs the weight gradient in partials mode, which the fused form does not have."""
+        if self.wgrad_apply_off or self.debug is not None or self.deterministic:
+            return False
+        src = rec.src
+        d = L.WgradDesc(self.dt, rec.n, rec.h, rec.w, src.c0, src.c1, rec.cout, 9, _xf(src.bn0), _xf(src.bn1), L.IN_PLAIN)
+        return bool(L.lib().oct_conv_wgrad_apply_store_ok(C.byref(d)))
+
+    def _conv_backward(self, rec: ConvRec, dy, G, accumulate, need_dx=True, apply_coef=None):
+        """dW of the conv (into G) and, if needed, the gradient(s) wrt its (virtually concatenated) input.
+        apply_coef (_wgrad_applies): `dy` holds dA; the weight-gradient launch forms dY from it and writes it back in place,
+        and the data gradient, which runs after it, reads dY."""
         n, h, w = rec.n, rec.h, rec.w
         src = rec.src
         cin = src.channels
-        dwp = self._wgrad(src, dy, rec.cout, 9, n, h, w)
+        if apply_coef is not None:
+            dwp = self._wgrad(src, dy, rec.cout, 9, n, h, w, fused_apply=(rec.y, apply_coef, rec.bn.scale, rec.bn.shift), dy_out=dy)
+        else:
+            dwp = self._wgrad(src, dy, rec.cout, 9, n, h, w)
         self._unpack(L.PACK_CONV_FPROP, dwp, G[rec.wkey], rec.cout, cin, accumulate)
         if not need_dx:
             return None, None
@@ -594,12 +620,12 @@ class UNetEngine:
         self._unpack(L.PACK_CONV_FPROP, dwp, G[r2.wkey], cout, cin, accumulate)
         return da1, parts
 
-    def _block_backward(self, name, da, dpool, G, accumulate, need_dx=True, partials=None):
+    def _block_backward(self, name, da, dpool, G, accumulate, need_dx=True, partials=None, head_dl=None):
         r1, r2 = self._ctx.convs[name]
         for r in (r1, r2):
             if r.cbkey and not accumulate and not r.bn.frozen:
                 G[r.cbkey].zero_()   # a bias in front of a train-mode BatchNorm cancels in (y - mean): zero gradient
-        dy2 = self._bn_backward(r2, da, dpool, G, accumulate, partials=partials)
+        dy2 = self._bn_backward(r2, da, dpool, G, accumulate, partials=partials, head_dl=head_dl)
         fused = self._conv_backward_fused(r1, r2, dy2, G, accumulate)
         if fused is not None:
             # one launch gave dA1, dW2 and the BatchNorm-backward sums of conv1: no weight-gradient pass, no reduction pass
@@ -619,6 +645,9 @@ class UNetEngine:
                               fused_apply=(r1.y, coef, r1.bn.scale, r1.bn.shift))
             self._unpack(L.PACK_CONV_FPROP, dwp, G[r1.wkey], r1.cout, 1, accumulate)
             return None, None
+        if self._wgrad_applies(r1):
+            da1, coef = self._bn_backward(r1, da1, None, G, accumulate, partials=parts1, defer_apply=True)
+            return self._conv_backward(r1, da1, G, accumulate, need_dx=need_dx, apply_coef=coef)
         dy1 = self._bn_backward(r1, da1, None, G, accumulate, partials=parts1)
         return self._conv_backward(r1, dy1, G, accumulate, need_dx=need_dx)
 
@@ -677,6 +706,7 @@ class UNetEngine:
         bgrad, wgrad_t = G[sp.head_b], G[sp.head_w]
         fused_dw = False
         dl = None
+        head_dl = None
         if f == 32 and dlogits is None:
             # fused: dlogits + dA = W^T dlogits + bias / weight gradients + BN-backward partial sums in one pass over y
             fused_dw = ncls <= 8
@@ -686,16 +716,29 @@ class UNetEngine:
                     wgrad_t.zero_()
             if not fused_dw:
                 dl = self._act(n, h, w, ncls, dev)
-            da = self._act(n, h, w, f, dev)
             nb = lib.oct_head_blocks(C.byref(hd))
             head_partials = torch.empty((nb, 2, f), dtype=torch.float32, device=dev)
-            L.check(lib.oct_head_backward_fused(
-                C.byref(hd), rec.y.data_ptr(), rec.bn.scale.data_ptr(), rec.bn.shift.data_ptr(),
-                rec.bn.mean.data_ptr(), rec.bn.invstd.data_ptr(), hw.data_ptr(),
-                hb.data_ptr(), L.ptr(tgt), L.ptr(dc), w_ce, L.ptr(dprobs), L.ptr(dl), da.data_ptr(),
-                head_partials.data_ptr(), bgrad.data_ptr(), wgrad_t.data_ptr() if fused_dw else None,
-                L.ptr(ctx.loss_partials) if dprobs is None else None, _stream()),
-                "oct_head_backward_fused")
+            # the library decides whether the head hands 16 B of dlogits per pixel, not the 64-B dA row, to the BatchNorm
+            # backward of the last block (which then recomputes dA); the debug path records dA and keeps the tensor
+            if (dprobs is None and not self.head_dl_off and self.debug is None
+                    and lib.oct_head_backward_dl_ok(C.byref(hd))):
+                da = None
+                dl8 = self._act(n, h, w, 8, dev)
+                head_dl = (hd, dl8, hw)
+                L.check(lib.oct_head_backward_dl(
+                    C.byref(hd), rec.y.data_ptr(), rec.bn.scale.data_ptr(), rec.bn.shift.data_ptr(),
+                    rec.bn.mean.data_ptr(), rec.bn.invstd.data_ptr(), hw.data_ptr(), hb.data_ptr(), tgt.data_ptr(),
+                    L.ptr(dc), w_ce, dl8.data_ptr(), head_partials.data_ptr(), bgrad.data_ptr(), wgrad_t.data_ptr(),
+                    L.ptr(ctx.loss_partials), _stream()), "oct_head_backward_dl")
+            else:
+                da = self._act(n, h, w, f, dev)
+                L.check(lib.oct_head_backward_fused(
+                    C.byref(hd), rec.y.data_ptr(), rec.bn.scale.data_ptr(), rec.bn.shift.data_ptr(),
+                    rec.bn.mean.data_ptr(), rec.bn.invstd.data_ptr(), hw.data_ptr(),
+                    hb.data_ptr(), L.ptr(tgt), L.ptr(dc), w_ce, L.ptr(dprobs), L.ptr(dl), da.data_ptr(),
+                    head_partials.data_ptr(), bgrad.data_ptr(), wgrad_t.data_ptr() if fused_dw else None,
+                    L.ptr(ctx.loss_partials) if dprobs is None else None, _stream()),
+                    "oct_head_backward_fused")
             if ctx.loss_partials is not None and dprobs is None:
                 w_ce_, w_dice_, eps_ = ctx.loss_cfg
                 L.check(lib.oct_head_loss_finalize(C.byref(hd), ctx.loss_partials.data_ptr(), ctx.loss_partials.shape[0],
@@ -725,7 +768,8 @@ class UNetEngine:
         dskip = [None] * nd
         for di in range(nd - 1, -1, -1):   # last decoder block first
             d0, d1 = self._block_backward(sp.dec[di].name, da, None, G, accumulate,
-                                          partials=head_partials if di == nd - 1 else None)
+                                          partials=head_partials if di == nd - 1 else None,
+                                          head_dl=head_dl if di == nd - 1 else None)
             du, dskip[di] = (d0, d1) if sp.dec_first else (d1, d0)
             wkey, bkey, cout_d = sp.ups[di]
             prev, u = ctx.ups[di]
