@@ -53,7 +53,7 @@ def _auc_on_device(y_true, y_pred):
     n = y_true.numel()
     ev = ScoreEvaluator(1, logits=False)
     ev.update(y_true.reshape(1, 1, 1, n), y_pred.reshape(1, 1, 1, n))
-    auc, nan, invalid = _auc_from_state(ev.state.cpu().numpy())
+    auc, nan, invalid = _auc_from_state(ev._host_state())
     if auc is None or invalid > 0 or nan > 0:
         return None   # sklearn decides what a missing class, a third label or a NaN score mean
     return np.float64(auc)

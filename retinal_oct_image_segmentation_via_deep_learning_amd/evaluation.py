@@ -1,11 +1,16 @@
-"""Streaming validation metrics with the state on the device (csrc/seg_eval.hip, oct_seg_eval_update).
+"""Streaming validation metrics with the state on the device.
 
 A validation loop scores batch after batch; `Metrics.evaluate(y_true, y_pred, classes=C)` reads its counts back per batch and
-knows neither a C x C confusion matrix nor ignore_index.  `SegEvaluator` keeps ONE int64 device buffer
+knows neither a C x C confusion matrix nor ignore_index.  The four evaluators here keep their result on the device: update()
+launches on the stream of its tensors' device and never synchronises, compute() is the only call that reads back, and there
+is no CPU fallback.  What they share is written once: `_Evaluator` (the device= argument and the three device rules of
+_bind), `_StateEvaluator` (one summable int64 state: state, reset, all_reduce, _host_state -- SegEvaluator, ScoreEvaluator,
+LesionEvaluator; BoundaryEvaluator's records are per image and not summable) and the plain functions below it for class-map
+pairs, image chunks under a workspace limit, the cached workspace and the model dispatch of update_model.
+
+Confusion matrix and thickness (csrc/seg_eval.hip, oct_seg_eval_update): `SegEvaluator` ADDS to one int64 buffer per update
 
     cm[t*C + p] | thick_abs[c] | columns | ignored | invalid | updates            (C*C + C + 4 entries)
-
-which every update() ADDS to with one kernel launch and no host synchronisation; compute() is the only call that reads it.
 
   ignored   has ignore_index and t == ignore_index: counted there and nowhere else
   invalid   not ignored, t or p outside [0, C): counted there and nowhere else
@@ -72,25 +77,44 @@ def state_size(classes: int) -> int:
     return classes * classes + classes + L.EVAL_STATE_EXTRA
 
 
+def _check_int(name, value, lo, hi, none_ok=False, out_of_range=None):
+    """value is an int (not a bool) in [lo, hi], or None where none_ok; out_of_range replaces the range message"""
+    if value is None and none_ok:
+        return
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise TypeError(f"{name} must be an int{' or None' if none_ok else ''}, got {type(value).__name__} {value!r}")
+    if not lo <= value <= hi:
+        raise ValueError(out_of_range or f"{name} must be in {lo}..{hi} (got {value})")
+
+
 def _check_config(classes, ignore_index):
-    if isinstance(classes, bool) or not isinstance(classes, int):
-        raise TypeError(f"classes must be an int, got {type(classes).__name__} {classes!r}")
-    if not 1 <= classes <= L.MAX_CLASSES:
-        raise ValueError(f"classes must be in 1..{L.MAX_CLASSES} (got {classes})")
-    if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
-        raise TypeError(f"ignore_index must be an int or None, got {type(ignore_index).__name__} {ignore_index!r}")
-    if ignore_index is not None and not -2 ** 63 <= ignore_index < 2 ** 63:
-        raise ValueError(f"ignore_index {ignore_index} is not an int64")
+    _check_int("classes", classes, 1, L.MAX_CLASSES)
+    _check_int("ignore_index", ignore_index, -2 ** 63, 2 ** 63 - 1, True, f"ignore_index {ignore_index} is not an int64")
+
+
+def _check_connectivity(connectivity):
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+
+
+def _check_workspace_limit(max_workspace_bytes):
+    if isinstance(max_workspace_bytes, bool) or not isinstance(max_workspace_bytes, int) or max_workspace_bytes < 1:
+        raise ValueError(f"max_workspace_bytes must be a positive int, got {max_workspace_bytes!r}")
+
+
+def _int_state(state, size, what):
+    """an evaluator's state as a flat int64 array of exactly `size` entries; `what` names the configuration in the message"""
+    s = np.asarray(state)
+    if s.dtype.kind not in "iu" or s.size != size:
+        raise ValueError(f"state must hold {size} integers for {what}, got {s.dtype} x {s.size}")
+    return s.astype(np.int64).reshape(-1)
 
 
 def metrics_from_state(state, classes: int) -> dict:
     """Every metric of the evaluator from its int64 state (numpy, no GPU): see SegEvaluator.compute."""
     from .Metrics import _formulas
     _check_config(classes, None)
-    s = np.asarray(state)
-    if s.dtype.kind not in "iu" or s.size != state_size(classes):
-        raise ValueError(f"state must hold {state_size(classes)} integers for {classes} classes, got {s.dtype} x {s.size}")
-    s = s.astype(np.int64).reshape(-1)
+    s = _int_state(state, state_size(classes), f"{classes} classes")
     cc = classes * classes
     cm = s[:cc].reshape(classes, classes).copy()
     thick = s[cc:cc + classes]
@@ -127,28 +151,93 @@ def _class_map(t, what):
     return t.contiguous()
 
 
-class SegEvaluator:
-    """Confusion matrix + per-layer thickness error of a validation set, accumulated on the device."""
+def _elem(t):
+    """the kernels' element code of a class map: uint8 (0) or int64 (2)"""
+    return 0 if t.dtype == torch.uint8 else 2
 
-    def __init__(self, classes, ignore_index=None, device=None):
-        _check_config(classes, ignore_index)
-        self.classes = classes
-        self.ignore_index = ignore_index
+
+def _map_geometry(m, max_dim=None, limit_what=None):
+    """(images, h, w) of a class map (..., H, W): H, W >= 1 and, with max_dim, at most that"""
+    h, w = m.shape[-2:]
+    if h < 1 or w < 1:
+        raise RuntimeError(f"class maps need H, W >= 1, got {tuple(m.shape)}")
+    if max_dim is not None and (h > max_dim or w > max_dim):
+        raise RuntimeError(f"{limit_what} take H, W <= {max_dim}, got {h} x {w}")
+    return m.numel() // (h * w), h, w
+
+
+def _class_map_pair(target, pred, max_dim=None, limit_what=None):
+    """Two integer class maps of one shape on one device as the kernels read them, and (images, h, w).  No device rule is
+    applied here: that is the evaluator's _bind, after every check that needs no device."""
+    target, pred = _class_map(target, "target"), _class_map(pred, "pred")
+    if target.shape != pred.shape:
+        raise RuntimeError(f"target {tuple(target.shape)} and pred {tuple(pred.shape)} must have the same shape")
+    if target.device != pred.device:
+        raise RuntimeError(f"target is on {target.device}, pred on {pred.device}")
+    return target, pred, _map_geometry(target, max_dim, limit_what)
+
+
+def _image_chunks(images, h, w, one, max_workspace_bytes):
+    """(lo, k) over images >= 1 in order: k images from lo on, the largest k whose workspace fits max_workspace_bytes given
+    that one image takes `one` bytes (bytes(k) <= k * bytes(1)) and whose k * h * w stays below 2^31.  An image that does not
+    fit raises here, before the first chunk is asked for."""
+    if one > max_workspace_bytes:
+        raise RuntimeError(f"one {h} x {w} image needs a workspace of {one} bytes, max_workspace_bytes is {max_workspace_bytes}")
+    per = min(images, max_workspace_bytes // one, max(1, (2 ** 31 - 1) // (h * w)))
+    return ((lo, min(per, images - lo)) for lo in range(0, images, per))
+
+
+def _grown(buf, need, device):
+    """the cached uint8 workspace `buf`, or a new one where it is missing, too small or on another device"""
+    if buf is None or buf.numel() < need or buf.device != device:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    return buf
+
+
+def _model_kind(model):
+    """(classes, hands_out_logits) of one of this package's networks: the logits networks (SegLossMixin) write NHWC logits,
+    the engine networks (UNet, BioUNet, UNet3D) answer through predict() / logits()"""
+    from .losses import SegLossMixin
+    from .unet import _EngineNet
+    if isinstance(model, SegLossMixin):
+        return model._classes(), True
+    if isinstance(model, _EngineNet):
+        return model._engine.ncls, False
+    raise TypeError(f"update_model takes one of this package's networks, got {type(model).__name__}")
+
+
+class _Evaluator:
+    """What every evaluator shares: the device= argument and the device rules of its inputs."""
+
+    def __init__(self, device):
         self.device = torch.device(device) if device is not None else None
         if self.device is not None and self.device.type != "cuda":
-            raise L.OctError("SegEvaluator needs a GPU device: there is no CPU fallback on the product path")
-        self.state = None   # int64 [C*C + C + 4] on the device, allocated by the first update
+            raise L.OctError(f"{type(self).__name__} needs a GPU device: there is no CPU fallback on the product path")
 
-    # ---- state ------------------------------------------------------------------------------------------------------------
-    def _state_on(self, device):
+    def _bind(self, device, held, what):
+        """`device` (that of the inputs) is a GPU, the one the evaluator was made for, and the one of the tensor it already
+        holds (`held`, named `what` in the message; None before the first update)"""
         if device.type != "cuda":
             raise L.OctError("the HIP path needs a device tensor (there is no CPU fallback)")
+        if self.device is not None and self.device.index is not None and device != self.device:
+            raise RuntimeError(f"inputs are on {device}, the evaluator was made for {self.device}")
+        if held is not None and held.device != device:
+            raise RuntimeError(f"inputs are on {device}, the evaluator's {what} on {held.device}")
+
+
+class _StateEvaluator(_Evaluator):
+    """An evaluator whose result is one int64 device buffer of `size` entries that every update ADDS to, so that the states
+    of several ranks sum."""
+
+    def __init__(self, device, size):
+        super().__init__(device)
+        self._size = size
+        self.state = None   # int64 [size] on the device, allocated by the first update
+
+    def _state_on(self, device):
+        self._bind(device, self.state, "state")
         if self.state is None:
-            if self.device is not None and self.device.index is not None and device != self.device:
-                raise RuntimeError(f"inputs are on {device}, the evaluator was made for {self.device}")
-            self.state = torch.zeros(state_size(self.classes), dtype=torch.int64, device=device)
-        elif self.state.device != device:
-            raise RuntimeError(f"inputs are on {device}, the evaluator's state on {self.state.device}")
+            self.state = torch.zeros(self._size, dtype=torch.int64, device=device)
         return self.state
 
     def reset(self):
@@ -156,29 +245,47 @@ class SegEvaluator:
             self.state.zero_()
         return self
 
+    def all_reduce(self, group=None):
+        """Sum the state over the ranks of `group` (one SUM all-reduce of the int64 state); nothing to do in one process."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return self
+        if self.state is None:   # a rank without a batch still takes part
+            self._state_on(self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device()))
+        dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
+        return self
+
+    def _host_state(self):
+        """the state as a numpy array (zeros before the first update): the one synchronisation"""
+        if self.state is None:
+            return np.zeros(self._size, dtype=np.int64)
+        return self.state.cpu().numpy()
+
+
+class SegEvaluator(_StateEvaluator):
+    """Confusion matrix + per-layer thickness error of a validation set, accumulated on the device."""
+
+    def __init__(self, classes, ignore_index=None, device=None):
+        _check_config(classes, ignore_index)
+        super().__init__(device, state_size(classes))
+        self.classes = classes
+        self.ignore_index = ignore_index
+
     def _launch(self, target, pred, kind, images, h, w):
         if images * h * w >= 2 ** 31:
             raise RuntimeError(f"one update takes fewer than 2^31 pixels, got {images} x {h} x {w}")
         state = self._state_on(target.device)
-        desc = L.SegEvalDesc(images, h, w, self.classes, 0 if target.dtype == torch.uint8 else 2, kind,
+        desc = L.SegEvalDesc(images, h, w, self.classes, _elem(target), kind,
                              int(self.ignore_index is not None), int(self.ignore_index or 0))
         L.check(L.lib().oct_seg_eval_update(C.byref(desc), target.data_ptr(), pred.data_ptr(), state.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream), "oct_seg_eval_update")
+                                            torch.cuda.current_stream(target.device).cuda_stream), "oct_seg_eval_update")
         return self
 
     # ---- updates ----------------------------------------------------------------------------------------------------------
     def update(self, target, pred):
         """Two integer class maps of one shape (..., H, W): uint8 and int64 are read as they are (each side its own type),
         other integer dtypes are converted to int64.  Every leading dimension counts images."""
-        target, pred = _class_map(target, "target"), _class_map(pred, "pred")
-        if target.shape != pred.shape:
-            raise RuntimeError(f"target {tuple(target.shape)} and pred {tuple(pred.shape)} must have the same shape")
-        if target.device != pred.device:
-            raise RuntimeError(f"target is on {target.device}, pred on {pred.device}")
-        h, w = target.shape[-2:]
-        if h < 1 or w < 1:
-            raise RuntimeError(f"class maps need H, W >= 1, got {tuple(target.shape)}")
-        images = target.numel() // (h * w)
+        target, pred, (images, h, w) = _class_map_pair(target, pred)
         kind = L.EVAL_PRED_U8 if pred.dtype == torch.uint8 else L.EVAL_PRED_I64
         return self._launch(target, pred, kind, images, h, w)
 
@@ -217,14 +324,7 @@ class SegEvaluator:
         """Forward of `model` in its current mode, then one update: the engine networks (UNet, BioUNet, UNet3D) through
         model.predict(x) -- a UNet3D map (B, D, H, W) counts B*D images -- the logits networks (SegLossMixin) straight from
         their NHWC logits."""
-        from .losses import SegLossMixin
-        from .unet import _EngineNet
-        if isinstance(model, SegLossMixin):
-            ncls, logits_net = model._classes(), True
-        elif isinstance(model, _EngineNet):
-            ncls, logits_net = model._engine.ncls, False
-        else:
-            raise TypeError(f"update_model takes one of this package's networks, got {type(model).__name__}")
+        ncls, logits_net = _model_kind(model)
         if ncls != self.classes:
             raise RuntimeError(f"{type(model).__name__} has {ncls} classes, the evaluator {self.classes}")
         if not torch.is_tensor(x) or x.dim() < 4:
@@ -239,26 +339,13 @@ class SegEvaluator:
             return self.update_logits(target, model._run_logits(x), "nhwc")
         return self.update(target, model.predict(x))
 
-    # ---- results ----------------------------------------------------------------------------------------------------------
-    def all_reduce(self, group=None):
-        """Sum the state over the ranks of `group` (one all-reduce of C*C + C + 4 int64); nothing to do in one process."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-            return self
-        if self.state is None:   # a rank without a batch still takes part
-            self._state_on(self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device()))
-        dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
-        return self
-
     def compute(self) -> dict:
         """The only call that synchronises: reads the state and returns
           confusion [C, C] int64; counts [C, 6] int64 = tp, t, p, tn, fp, fn one-vs-rest with n = valid pixels;
           every key of Metrics._formulas as a float64 array over the classes; pixel_accuracy; present = t + p > 0;
           mean_dice / mean_iou over the present classes; thickness_error = thick_abs / columns in pixels (NaN without a
           column); n, ignored, invalid, columns, updates."""
-        if self.state is None:
-            return metrics_from_state(np.zeros(state_size(self.classes), dtype=np.int64), self.classes)
-        return metrics_from_state(self.state.cpu().numpy(), self.classes)
+        return metrics_from_state(self._host_state(), self.classes)
 
 
 # ---- contour metrics ------------------------------------------------------------------------------------------------------
@@ -297,34 +384,22 @@ def contour_metrics_from_records(records) -> dict:
     return res
 
 
-class BoundaryEvaluator:
+class BoundaryEvaluator(_Evaluator):
     """Hausdorff / HD95 / ASSD per image and class of a validation set; the records stay on the device until compute()."""
 
     def __init__(self, classes, ignore_index=None, device=None, max_workspace_bytes=256 << 20):
         _check_config(classes, ignore_index)
-        if isinstance(max_workspace_bytes, bool) or not isinstance(max_workspace_bytes, int) or max_workspace_bytes < 1:
-            raise ValueError(f"max_workspace_bytes must be a positive int, got {max_workspace_bytes!r}")
+        _check_workspace_limit(max_workspace_bytes)
+        super().__init__(device)
         self.classes = classes
         self.ignore_index = ignore_index
         self.max_workspace_bytes = max_workspace_bytes
-        self.device = torch.device(device) if device is not None else None
-        if self.device is not None and self.device.type != "cuda":
-            raise L.OctError("BoundaryEvaluator needs a GPU device: there is no CPU fallback on the product path")
         self._chunks = []        # int64 [images_i, C, 2, 5] device tensors, in update order
         self._workspace = None   # uint8 device buffer, grown on demand, reused by every update
 
     def _desc(self, images, h, w, target, pred):
-        return L.ContourDesc(images, h, w, self.classes, 0 if target.dtype == torch.uint8 else 2,
-                             0 if pred.dtype == torch.uint8 else 2, int(self.ignore_index is not None),
+        return L.ContourDesc(images, h, w, self.classes, _elem(target), _elem(pred), int(self.ignore_index is not None),
                              int(self.ignore_index or 0))
-
-    def _check_device(self, device):
-        if device.type != "cuda":
-            raise L.OctError("the HIP path needs a device tensor (there is no CPU fallback)")
-        if self.device is not None and self.device.index is not None and device != self.device:
-            raise RuntimeError(f"inputs are on {device}, the evaluator was made for {self.device}")
-        if self._chunks and self._chunks[0].device != device:
-            raise RuntimeError(f"inputs are on {device}, the evaluator's records on {self._chunks[0].device}")
 
     def reset(self):
         self._chunks = []
@@ -334,37 +409,22 @@ class BoundaryEvaluator:
         """Two integer class maps of one shape (..., H, W), H, W <= 16384, with SegEvaluator.update's input rules.  The batch
         goes through the kernel in chunks of images whose workspace fits max_workspace_bytes; one image that does not fit
         raises.  Nothing is read back."""
-        target, pred = _class_map(target, "target"), _class_map(pred, "pred")
-        if target.shape != pred.shape:
-            raise RuntimeError(f"target {tuple(target.shape)} and pred {tuple(pred.shape)} must have the same shape")
-        if target.device != pred.device:
-            raise RuntimeError(f"target is on {target.device}, pred on {pred.device}")
-        h, w = target.shape[-2:]
-        if h < 1 or w < 1:
-            raise RuntimeError(f"class maps need H, W >= 1, got {tuple(target.shape)}")
-        if h > L.CONTOUR_MAX_DIM or w > L.CONTOUR_MAX_DIM:
-            raise RuntimeError(f"contour metrics take H, W <= {L.CONTOUR_MAX_DIM}, got {h} x {w}")
-        self._check_device(target.device)
-        images = target.numel() // (h * w)
+        target, pred, (images, h, w) = _class_map_pair(target, pred, L.CONTOUR_MAX_DIM, "contour metrics")
+        self._bind(target.device, self._chunks[0] if self._chunks else None, "records")
         if images == 0:
             return self
         lib = L.lib()
         one = int(lib.oct_contour_workspace_bytes(C.byref(self._desc(1, h, w, target, pred))))
         if one == 0:
             raise L.OctError(f"oct_contour_workspace_bytes failed: {L.last_error()}")
-        if one > self.max_workspace_bytes:
-            raise RuntimeError(f"one {h} x {w} image with {self.classes} classes needs a workspace of {one} bytes, "
-                               f"max_workspace_bytes is {self.max_workspace_bytes}")
-        per = min(images, self.max_workspace_bytes // one, max(1, (2 ** 31 - 1) // (h * w)))   # bytes(k) <= k * bytes(1)
+        chunks = _image_chunks(images, h, w, one, self.max_workspace_bytes)
         target, pred = target.reshape(images, h, w), pred.reshape(images, h, w)
         out = torch.empty((images, self.classes, 2, len(RECORD_FIELDS)), dtype=torch.int64, device=target.device)
         stream = torch.cuda.current_stream(target.device).cuda_stream
-        for lo in range(0, images, per):
-            k = min(per, images - lo)
+        for lo, k in chunks:
             desc = self._desc(k, h, w, target, pred)
             need = int(lib.oct_contour_workspace_bytes(C.byref(desc)))
-            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != target.device:
-                self._workspace = torch.empty(need, dtype=torch.uint8, device=target.device)
+            self._workspace = _grown(self._workspace, need, target.device)
             L.check(lib.oct_contour_update(C.byref(desc), target[lo:lo + k].data_ptr(), pred[lo:lo + k].data_ptr(),
                                            out[lo:lo + k].data_ptr(), self._workspace.data_ptr(), stream), "oct_contour_update")
         self._chunks.append(out)
@@ -374,12 +434,12 @@ class BoundaryEvaluator:
     def update_model(self, model, x, target):
         """model.predict(x) of an engine network (UNet, BioUNet, UNet3D) against target; the logits networks have no class
         map of their own: pass theirs to update(target, class_map)."""
-        from .unet import _EngineNet
-        if not isinstance(model, _EngineNet):
+        ncls, logits_net = _model_kind(model)
+        if logits_net:
             raise TypeError(f"update_model takes an engine network with predict(); for {type(model).__name__} call "
                             "update(target, class_map) with its arg-max")
-        if model._engine.ncls != self.classes:
-            raise RuntimeError(f"{type(model).__name__} has {model._engine.ncls} classes, the evaluator {self.classes}")
+        if ncls != self.classes:
+            raise RuntimeError(f"{type(model).__name__} has {ncls} classes, the evaluator {self.classes}")
         return self.update(target, model.predict(x))
 
     def merge(self, records):
@@ -440,22 +500,14 @@ def key_value(k):
 
 
 def _check_score_config(channels, ignore_value):
-    if isinstance(channels, bool) or not isinstance(channels, int):
-        raise TypeError(f"channels must be an int, got {type(channels).__name__} {channels!r}")
-    if not 1 <= channels <= L.MAX_CLASSES:
-        raise ValueError(f"channels must be in 1..{L.MAX_CLASSES} (got {channels})")
-    if ignore_value is not None and (isinstance(ignore_value, bool) or not isinstance(ignore_value, int)):
-        raise TypeError(f"ignore_value must be an int or None, got {type(ignore_value).__name__} {ignore_value!r}")
-    if ignore_value is not None and not 2 <= ignore_value <= 255:
-        raise ValueError(f"ignore_value {ignore_value} is not in [2, 255] (0 and 1 are the mask's own values)")
+    _check_int("channels", channels, 1, L.MAX_CLASSES)
+    _check_int("ignore_value", ignore_value, 2, 255, True,
+               f"ignore_value {ignore_value} is not in [2, 255] (0 and 1 are the mask's own values)")
 
 
 def _score_hist(state, channels):
     _check_score_config(channels, None)
-    s = np.asarray(state)
-    if s.dtype.kind not in "iu" or s.size != score_state_size(channels):
-        raise ValueError(f"state must hold {score_state_size(channels)} integers for {channels} channels, got {s.dtype} x {s.size}")
-    s = s.astype(np.int64).reshape(-1)
+    s = _int_state(state, score_state_size(channels), f"{channels} channels")
     nh = channels * 2 * SCORE_KEYS
     return s[:nh].reshape(channels, 2, SCORE_KEYS), s[nh:]
 
@@ -578,13 +630,12 @@ def score_metrics_from_state(state, channels: int, thresholds=(0.5,), logits=Tru
     return res
 
 
-class ScoreEvaluator:
+class ScoreEvaluator(_StateEvaluator):
     """Threshold-free validation of a binary / multi-label head, accumulated on the device (csrc/score_eval.hip): per channel
-    ONE [2][65536] histogram of key16(score) by label in an int64 buffer
+    ONE [2][65536] histogram of key16(score) by label in the int64 state
 
         hist[C][2][65536] | nan[C] | ignored[C] | invalid[C] | updates
 
-    which every update() ADDS to with one kernel launch and no host synchronisation; compute() is the only call that reads it.
     Each element goes to one place: ignored (ignore_value given and t == ignore_value), else invalid (t > 1), else nan (the
     score is NaN), else hist[c][t][key16(score)].
 
@@ -600,29 +651,10 @@ class ScoreEvaluator:
 
     def __init__(self, channels, ignore_value=None, logits=True, device=None):
         _check_score_config(channels, ignore_value)
+        super().__init__(device, score_state_size(channels))
         self.channels = channels
         self.ignore_value = ignore_value
         self.logits = bool(logits)
-        self.device = torch.device(device) if device is not None else None
-        if self.device is not None and self.device.type != "cuda":
-            raise L.OctError("ScoreEvaluator needs a GPU device: there is no CPU fallback on the product path")
-        self.state = None   # int64 [C * (2 * 65536 + 3) + 1] on the device, allocated by the first update
-
-    def _state_on(self, device):
-        if device.type != "cuda":
-            raise L.OctError("the HIP path needs a device tensor (there is no CPU fallback)")
-        if self.state is None:
-            if self.device is not None and self.device.index is not None and device != self.device:
-                raise RuntimeError(f"inputs are on {device}, the evaluator was made for {self.device}")
-            self.state = torch.zeros(score_state_size(self.channels), dtype=torch.int64, device=device)
-        elif self.state.device != device:
-            raise RuntimeError(f"inputs are on {device}, the evaluator's state on {self.state.device}")
-        return self.state
-
-    def reset(self):
-        if self.state is not None:
-            self.state.zero_()
-        return self
 
     def _launch(self, target, scores, images, h, w):
         """target uint8 and scores, both contiguous [images][channels][h][w] on one device"""
@@ -682,17 +714,10 @@ class ScoreEvaluator:
         """Forward of `model` in its current mode, then one update on its logits: the engine networks (UNet, BioUNet) through
         model.logits(x) (NCHW fp32), the logits networks (SegLossMixin) through their NHWC logits.  UNet3D is refused: the
         binary head is 2-D only."""
-        from .losses import SegLossMixin
-        from .unet import _EngineNet
-        if isinstance(model, SegLossMixin):
-            ncls, logits_net = model._classes(), True
-        elif isinstance(model, _EngineNet):
-            if not model._weighted_loss:
-                raise NotImplementedError(f"{type(model).__name__}: the binary / multi-label head is implemented for the 2-D "
-                                          "networks only")
-            ncls, logits_net = model._engine.ncls, False
-        else:
-            raise TypeError(f"update_model takes one of this package's networks, got {type(model).__name__}")
+        ncls, logits_net = _model_kind(model)
+        if not logits_net and not model._weighted_loss:
+            raise NotImplementedError(f"{type(model).__name__}: the binary / multi-label head is implemented for the 2-D "
+                                      "networks only")
         if ncls != self.channels:
             raise RuntimeError(f"{type(model).__name__} has {ncls} output channels, the evaluator {self.channels}")
         if not torch.is_tensor(x) or x.dim() != 4:
@@ -703,21 +728,6 @@ class ScoreEvaluator:
         if logits_net:
             return self.update(target, model._run_logits(x), "nhwc")
         return self.update(target, model.logits(x), "nchw")
-
-    def all_reduce(self, group=None):
-        """Sum the state over the ranks of `group` (one SUM all-reduce of the int64 state); nothing to do in one process."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-            return self
-        if self.state is None:   # a rank without a batch still takes part
-            self._state_on(self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device()))
-        dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
-        return self
-
-    def _host_state(self):
-        if self.state is None:
-            return np.zeros(score_state_size(self.channels), dtype=np.int64)
-        return self.state.cpu().numpy()
 
     def compute(self, thresholds=(0.5,)) -> dict:
         """The only call that synchronises: score_metrics_from_state on the state, thresholds as probabilities."""
@@ -761,10 +771,7 @@ def lesion_metrics_from_state(state, classes: int) -> dict:
       f1 = 2 sensitivity precision / (sensitivity + precision)   float64 [C]; a 0 / 0 is NaN, f1 is NaN where either is NaN and 0
       where both are 0;   images, ignored, invalid, updates   int."""
     _check_config(classes, None)
-    s = np.asarray(state)
-    if s.dtype.kind not in "iu" or s.size != lesion_state_size(classes):
-        raise ValueError(f"state must hold {lesion_state_size(classes)} integers for {classes} classes, got {s.dtype} x {s.size}")
-    s = s.astype(np.int64).reshape(-1)
+    s = _int_state(state, lesion_state_size(classes), f"{classes} classes")
     counts = s[:classes * 4].reshape(classes, 4)
     nt, npred, det, conf = (counts[:, k].copy() for k in range(4))
     nan = np.float64("nan")
@@ -778,89 +785,52 @@ def lesion_metrics_from_state(state, classes: int) -> dict:
             "images": images, "ignored": ignored, "invalid": invalid, "updates": updates}
 
 
-class LesionEvaluator:
+class LesionEvaluator(_StateEvaluator):
     """Lesion-wise detection scores of a validation set (csrc/components.hip, oct_lesion_eval_update): both maps are labelled
     into connected components (same value, 4- or 8-neighbours); a target component G of class c is DETECTED when
     inter(G) = #{pixels of G with pred == c} >= 1 and inter(G) * den >= num * area(G), num / den = min_overlap; a predicted
     component is CONFIRMED by the same rule with the roles swapped.  A pixel whose target equals ignore_index is outside in both
-    maps, so it splits a predicted component that runs through it.  One int64 device buffer
+    maps, so it splits a predicted component that runs through it.  The int64 state is
 
         [classes][target_components, pred_components, detected, confirmed] | images | ignored | invalid | updates
 
-    which every update() ADDS to without a host synchronisation; compute() is the only call that reads it.  A batch goes through
-    the kernels in chunks of images whose workspace (26 bytes per pixel) fits max_workspace_bytes."""
+    A batch goes through the kernels in chunks of images whose workspace (26 bytes per pixel) fits max_workspace_bytes."""
 
     def __init__(self, classes, connectivity=4, ignore_index=None, min_overlap=(0, 1), device=None, max_workspace_bytes=256 << 20):
         _check_config(classes, ignore_index)
-        if isinstance(connectivity, bool) or connectivity not in (4, 8):
-            raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
-        if isinstance(max_workspace_bytes, bool) or not isinstance(max_workspace_bytes, int) or max_workspace_bytes < 1:
-            raise ValueError(f"max_workspace_bytes must be a positive int, got {max_workspace_bytes!r}")
+        _check_connectivity(connectivity)
+        _check_workspace_limit(max_workspace_bytes)
         self.min_overlap = _check_overlap(min_overlap)
+        super().__init__(device, lesion_state_size(classes))
         self.classes = classes
         self.connectivity = connectivity
         self.ignore_index = ignore_index
         self.max_workspace_bytes = max_workspace_bytes
-        self.device = torch.device(device) if device is not None else None
-        if self.device is not None and self.device.type != "cuda":
-            raise L.OctError("LesionEvaluator needs a GPU device: there is no CPU fallback on the product path")
-        self.state = None        # int64 [C*4 + 4] on the device, allocated by the first update
         self._workspace = None   # uint8 device buffer, grown on demand, reused by every update
 
-    def _state_on(self, device):
-        if device.type != "cuda":
-            raise L.OctError("the HIP path needs a device tensor (there is no CPU fallback)")
-        if self.state is None:
-            if self.device is not None and self.device.index is not None and device != self.device:
-                raise RuntimeError(f"inputs are on {device}, the evaluator was made for {self.device}")
-            self.state = torch.zeros(lesion_state_size(self.classes), dtype=torch.int64, device=device)
-        elif self.state.device != device:
-            raise RuntimeError(f"inputs are on {device}, the evaluator's state on {self.state.device}")
-        return self.state
-
-    def reset(self):
-        if self.state is not None:
-            self.state.zero_()
-        return self
-
     def _desc(self, images, h, w, target, pred):
-        return L.CcDesc(images, h, w, self.classes, 0 if target.dtype == torch.uint8 else 2, 0 if pred.dtype == torch.uint8 else 2,
-                        self.connectivity, L.CC_OP_LESION, int(self.ignore_index is not None), self.min_overlap[0],
-                        self.min_overlap[1], 0, int(self.ignore_index or 0))
+        return L.CcDesc(images, h, w, self.classes, _elem(target), _elem(pred), self.connectivity, L.CC_OP_LESION,
+                        int(self.ignore_index is not None), self.min_overlap[0], self.min_overlap[1], 0,
+                        int(self.ignore_index or 0))
 
     def update(self, target, pred):
         """Two integer class maps of one shape (..., H, W), H, W <= 16384, with SegEvaluator.update's input rules.  One image
         whose workspace does not fit max_workspace_bytes raises.  Nothing is read back."""
-        target, pred = _class_map(target, "target"), _class_map(pred, "pred")
-        if target.shape != pred.shape:
-            raise RuntimeError(f"target {tuple(target.shape)} and pred {tuple(pred.shape)} must have the same shape")
-        if target.device != pred.device:
-            raise RuntimeError(f"target is on {target.device}, pred on {pred.device}")
-        h, w = target.shape[-2:]
-        if h < 1 or w < 1:
-            raise RuntimeError(f"class maps need H, W >= 1, got {tuple(target.shape)}")
-        if h > L.CC_MAX_DIM or w > L.CC_MAX_DIM:
-            raise RuntimeError(f"connected components take H, W <= {L.CC_MAX_DIM}, got {h} x {w}")
+        target, pred, (images, h, w) = _class_map_pair(target, pred, L.CC_MAX_DIM, "connected components")
         state = self._state_on(target.device)
-        images = target.numel() // (h * w)
         if images == 0:
             return self
         lib = L.lib()
         one = int(lib.oct_cc_workspace_bytes(C.byref(self._desc(1, h, w, target, pred))))
         if one == 0:
             raise L.OctError(f"oct_cc_workspace_bytes failed: {L.last_error()}")
-        if one > self.max_workspace_bytes:
-            raise RuntimeError(f"one {h} x {w} image needs a workspace of {one} bytes, max_workspace_bytes is "
-                               f"{self.max_workspace_bytes}")
-        per = min(images, self.max_workspace_bytes // one, max(1, (2 ** 31 - 1) // (h * w)))   # bytes(k) <= k * bytes(1)
+        chunks = _image_chunks(images, h, w, one, self.max_workspace_bytes)
         target, pred = target.reshape(images, h, w), pred.reshape(images, h, w)
         stream = torch.cuda.current_stream(target.device).cuda_stream
-        for lo in range(0, images, per):
-            k = min(per, images - lo)
+        for lo, k in chunks:
             desc = self._desc(k, h, w, target, pred)
             need = int(lib.oct_cc_workspace_bytes(C.byref(desc)))
-            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != target.device:
-                self._workspace = torch.empty(need, dtype=torch.uint8, device=target.device)
+            self._workspace = _grown(self._workspace, need, target.device)
             L.check(lib.oct_lesion_eval_update(C.byref(desc), target[lo:lo + k].data_ptr(), pred[lo:lo + k].data_ptr(),
                                                state.data_ptr(), self._workspace.data_ptr(), stream), "oct_lesion_eval_update")
         return self
@@ -869,31 +839,12 @@ class LesionEvaluator:
     def update_model(self, model, x, target):
         """model.predict(x) of one of this package's networks in its current mode against target: the engine networks (UNet,
         BioUNet, UNet3D -- a (B, D, H, W) map counts B*D slice images) and the logits networks (SegLossMixin) alike."""
-        from .losses import SegLossMixin
-        from .unet import _EngineNet
-        if isinstance(model, SegLossMixin):
-            ncls = model._classes()
-        elif isinstance(model, _EngineNet):
-            ncls = model._engine.ncls
-        else:
-            raise TypeError(f"update_model takes one of this package's networks, got {type(model).__name__}")
+        ncls, _ = _model_kind(model)
         if ncls != self.classes:
             raise RuntimeError(f"{type(model).__name__} has {ncls} classes, the evaluator {self.classes}")
         return self.update(target, model.predict(x))
 
-    def all_reduce(self, group=None):
-        """Sum the state over the ranks of `group` (one all-reduce of C*4 + 4 int64); nothing to do in one process."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-            return self
-        if self.state is None:   # a rank without a batch still takes part
-            self._state_on(self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device()))
-        dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
-        return self
-
     def compute(self) -> dict:
         """The only call that synchronises: lesion_metrics_from_state on the state.  `updates` counts kernel calls, one per
         chunk of an update."""
-        if self.state is None:
-            return lesion_metrics_from_state(np.zeros(lesion_state_size(self.classes), dtype=np.int64), self.classes)
-        return lesion_metrics_from_state(self.state.cpu().numpy(), self.classes)
+        return lesion_metrics_from_state(self._host_state(), self.classes)

@@ -28,14 +28,9 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .evaluation import _check_config, _class_map
+from .evaluation import _check_config, _check_connectivity, _class_map, _elem, _grown, _map_geometry
 
 AREA_MASK = (1 << L.CC_BORDER_BIT) - 1
-
-
-def _check_connectivity(connectivity):
-    if isinstance(connectivity, bool) or connectivity not in (4, 8):
-        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
 
 
 def tile():
@@ -48,12 +43,7 @@ def tile():
 def _geometry(m, what="map"):
     """a class map as the kernels read it and (images, h, w)"""
     m = _class_map(m, what)
-    h, w = m.shape[-2:]
-    if h < 1 or w < 1:
-        raise RuntimeError(f"class maps need H, W >= 1, got {tuple(m.shape)}")
-    if h > L.CC_MAX_DIM or w > L.CC_MAX_DIM:
-        raise RuntimeError(f"connected components take H, W <= {L.CC_MAX_DIM}, got {h} x {w}")
-    images = m.numel() // (h * w)
+    images, h, w = _map_geometry(m, L.CC_MAX_DIM, "connected components")
     if images * h * w >= 2 ** 31:
         raise RuntimeError(f"one call takes fewer than 2^31 pixels, got {images} x {h} x {w}")
     return m, images, h, w
@@ -65,9 +55,8 @@ def _need_device(m):
 
 
 def _desc(images, h, w, classes, m, connectivity, ignore_index, op, pred=None, min_overlap=(0, 1)):
-    return L.CcDesc(images, h, w, classes, 0 if m.dtype == torch.uint8 else 2,
-                    0 if pred is None or pred.dtype == torch.uint8 else 2, connectivity, op, int(ignore_index is not None),
-                    min_overlap[0], min_overlap[1], 0, int(ignore_index or 0))
+    return L.CcDesc(images, h, w, classes, _elem(m), 0 if pred is None else _elem(pred), connectivity, op,
+                    int(ignore_index is not None), min_overlap[0], min_overlap[1], 0, int(ignore_index or 0))
 
 
 def _workspace_bytes(desc, what):
@@ -164,12 +153,6 @@ class ComponentFilter:
             self._rules.replace[c] = self.replace[c]
         self._workspace = None   # uint8 device buffer, grown on demand, reused by every call
 
-    def _workspace_for(self, desc, device):
-        need = _workspace_bytes(desc, "the filter")
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._workspace
-
     def __call__(self, map, out=None):
         """The filtered map: the input's shape and (after the conversion of connected_components) dtype.  `out` may be a
         tensor of that shape and dtype to write into -- the converted input itself for a filter in place."""
@@ -185,7 +168,7 @@ class ComponentFilter:
         if images == 0:
             return out
         desc = _desc(images, h, w, self.classes, m, self.connectivity, self.ignore_index, L.CC_OP_FILTER)
-        ws = self._workspace_for(desc, m.device)
+        ws = self._workspace = _grown(self._workspace, _workspace_bytes(desc, "the filter"), m.device)
         roots, info = _label(m, images, h, w, self.classes, self.connectivity, self.ignore_index, ws, L.CC_OP_FILTER)
         L.check(L.lib().oct_cc_filter(C.byref(desc), C.byref(self._rules), m.data_ptr(), roots.data_ptr(), info.data_ptr(),
                                       out.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(m.device).cuda_stream),

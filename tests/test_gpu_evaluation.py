@@ -142,6 +142,23 @@ def test_three_updates_accumulate_without_a_synchronisation_and_reset_zeroes():
     assert not _state(ev).any() and ev.compute()["updates"] == 0
 
 
+def test_updates_on_a_side_stream_are_ordered_on_that_stream():
+    """update and update_logits inside torch.cuda.stream(s): the state is allocated and both kernels run on s, the stream of
+    the tensors' device, so s.synchronize() alone makes the state readable.  Width 70: one full strip of 64 columns and a tail."""
+    E = _E()
+    t, p, ref = _maps((2, 5, 70), 3, "random", 255)
+    lg = np.random.default_rng(seed("side stream")).standard_normal((2, 5, 70, 3)).astype(np.float32)
+    dt, dp, dl = _dev(t, torch.uint8), _dev(p, torch.uint8), torch.from_numpy(lg).cuda()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())                   # the inputs were written on the default stream
+    ev = E.SegEvaluator(3, ignore_index=255)
+    with torch.cuda.stream(s):
+        ev.update(dt, dp).update_logits(dt, dl, "nhwc")
+    s.synchronize()
+    np.testing.assert_array_equal(_state(ev), ref + R.eval_state(t, R.argmax_first(lg, 3), 3, 255))
+    assert ev.compute()["updates"] == 2
+
+
 @pytest.mark.parametrize("classes", [2, 8, 11])
 def test_counts_equal_metrics_evaluate_and_thickness_equals_the_reference_function(classes):
     from retinal_oct_image_segmentation_via_deep_learning_amd import Metrics
