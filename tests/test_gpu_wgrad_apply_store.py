@@ -55,7 +55,7 @@ def operands(shape, exact):
     n, h, w = shape
     g = torch.Generator().manual_seed(31 * n + 7 * h + w + (1000 if exact else 0))
     npix = n * h * w
-    big = npix > 100000
+    big = npix > 50000      # thin dA, no k1 / k2: the sums of the exact case stay below 2^24 granules (asserted by the test)
 
     def choice(vals, size):
         return torch.tensor(vals)[torch.randint(0, len(vals), size, generator=g)]
