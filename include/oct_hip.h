@@ -916,6 +916,69 @@ int oct_cc_filter(const OctCcDesc* d, const OctCcRules* rules, const void* map, 
                   void* workspace, void* stream);
 int oct_lesion_eval_update(const OctCcDesc* d, const void* target, const void* pred, int64_t* state, void* workspace, void* stream);
 
+/* Distance maps (library 0.2.2, same OCT_VERSION): the exact squared Euclidean distance, in pixels, from every pixel of a class
+ * map [images][h][w], uint8 (elem 0) or int64 (elem 2), to the nearest site of each of a list of planes, and the two maps a
+ * training step makes of it.  All integer arithmetic up to the epilogue; every result is a pure function of the inputs: two runs
+ * give the same bits.
+ *   valid      a pixel whose value is in [0, classes) and (has_ignore) is not ignore_index.  An invalid pixel is a site of no
+ *              plane; it still receives a distance
+ *   sites      OCT_DT_BOUNDARY  valid pixels with a 4-neighbour INSIDE THE IMAGE that is valid and has another value (the image
+ *                               edge is no boundary, an invalid neighbour makes none)
+ *              OCT_DT_CLASS c   valid pixels equal to c            OCT_DT_OTHER c   valid pixels not equal to c
+ *   D2         int32: min over the sites (ys, xs) of the image of (y - ys)^2 + (x - xs)^2; 0 on a site; OCT_DT_FAR everywhere in
+ *              an image whose plane has no site.  h, w <= 16384 keeps every real value below OCT_DT_FAR
+ *
+ * oct_dt_squared(d, planes, map, out, workspace, stream)
+ *   planes  HOST memory, int32 [d->planes][2] = (OCT_DT_BOUNDARY / _CLASS / _OTHER, class); class in [0, classes), 0 for a
+ *           boundary plane.  1 <= d->planes <= OCT_DT_MAX_PLANES
+ *   out     int32 [images][planes][h][w], WRITTEN: D2
+ * oct_dt_weight_map(d, planes, map, table, table_len, out, workspace, stream)
+ *   table   fp32 [table_len] on the device, table_len >= 1, indexed by the SQUARED distance
+ *   out     fp32 [images][planes][h][w], WRITTEN: table[min(D2, table_len - 1)] -- a copy of the entry, so any profile of the
+ *           distance tabulated on the host is reproduced bit for bit; no int32 plane is written
+ * oct_dt_signed(d, class_ids, map, out, workspace, stream)
+ *   class_ids  HOST memory, int32 [d->planes], each in [0, classes); d->planes <= OCT_DT_MAX_PLANES / 2
+ *   out     fp32 [images][planes][h][w], WRITTEN: on a pixel of class c  -sqrtf(D2 to OCT_DT_OTHER c), on every other pixel
+ *           (invalid ones included)  +sqrtf(D2 to OCT_DT_CLASS c); the whole plane of an image is 0 where the class is absent
+ *           or nothing valid lies outside it.  D2 is converted to fp32 (exact below 2^24) and sqrtf is IEEE: one rounding
+ *
+ * workspace  oct_dt_workspace_bytes(d) bytes on the device for d->op, 16-byte aligned, contents irrelevant before and after.
+ *            With N = images*h*w, G = planes (signed: 2*planes), S = ceil(h/64) and A(x) = x rounded up to 256:
+ *              [A(N) for an int64 map] + A(2*G*N) + A(8*G*images*S*w) + A(4*G*images)
+ *            the map as bytes, the column distances, the column masks, the has-a-site flags.  0 for a descriptor the entry
+ *            points reject.  Each entry point uses the layout of its own op whatever d->op.
+ * oct_dt_block  rows: the rows one column-pass thread covers (one 64-bit site mask); cols: the pixels one row-pass workgroup
+ *            covers (whole rows where rows are shorter than that, a stretch of one row otherwise).  Shapes that straddle either
+ *            follow from it.
+ * Launches: [labels, int64 only] -> column masks -> column distances g (uint16) -> rows: the g rows of a workgroup in LDS in
+ * blocks of 16 columns with each block's smallest g; D2(x) = min over x' of (x - x')^2 + g[x']^2, taken over the columns next to
+ * x, then block by block outward while a block's nearest column is closer than sqrt(best), reading a block only where that
+ * distance squared plus its smallest g squared is below best: every column that could lower the minimum is read.
+ * A value is range-checked before it indexes anything.  The one atomic is the flag's atomicOr.  No allocation, no host
+ * synchronisation, only `stream`.  Any h, w in 1..16384, any element-aligned base; images*h*w < 2^31; images == 0 is a no-op. */
+#define OCT_DT_FAR (1 << 30)
+#define OCT_DT_MAX_PLANES 64
+#define OCT_DT_BOUNDARY 0
+#define OCT_DT_CLASS 1
+#define OCT_DT_OTHER 2
+#define OCT_DT_OP_SQUARED 0
+#define OCT_DT_OP_WEIGHT 1
+#define OCT_DT_OP_SIGNED 2
+typedef struct {
+  int images, h, w, classes; /* images = product of all leading dims; 1 <= classes <= 16; h, w <= 16384 */
+  int map_elem;              /* 0 uint8, 2 int64 */
+  int has_ignore;
+  int planes;                /* planes of the output: the plane list, or the class list of oct_dt_signed */
+  int op;                    /* OCT_DT_OP_*: which workspace oct_dt_workspace_bytes sizes */
+  int64_t ignore_index;
+} OctDtDesc;
+size_t oct_dt_workspace_bytes(const OctDtDesc* d);
+int oct_dt_block(int* rows, int* cols);
+int oct_dt_squared(const OctDtDesc* d, const int32_t* planes, const void* map, int32_t* out, void* workspace, void* stream);
+int oct_dt_weight_map(const OctDtDesc* d, const int32_t* planes, const void* map, const float* table, int table_len, float* out,
+                      void* workspace, void* stream);
+int oct_dt_signed(const OctDtDesc* d, const int32_t* class_ids, const void* map, float* out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,7 +104,17 @@ class CcRules(C.Structure):          # struct OctCcRules
     _fields_ = [("min_area", c_int * 16), ("keep_largest", c_int * 16), ("drop_enclosed", c_int * 16), ("replace", C.c_int64 * 16)]
 
 
+class DtDesc(C.Structure):           # struct OctDtDesc
+    _fields_ = [(k, c_int) for k in ("images", "h", "w", "classes", "map_elem", "has_ignore", "planes", "op")] + \
+               [("ignore_index", C.c_int64)]
+
+
 CC_OP_LABEL, CC_OP_FILTER, CC_OP_LESION = range(3)   # OCT_CC_OP_*
+DT_FAR = 1 << 30       # OCT_DT_FAR: the squared distance where an image has no site of the plane
+DT_MAX_PLANES = 64     # OCT_DT_MAX_PLANES; oct_dt_signed takes half as many classes
+DT_MAX_DIM = 16384     # h, w of the distance-map entry points
+DT_BOUNDARY, DT_CLASS, DT_OTHER = range(3)   # OCT_DT_* plane kinds
+DT_OP_SQUARED, DT_OP_WEIGHT, DT_OP_SIGNED = range(3)   # OCT_DT_OP_*
 CC_BORDER_BIT = 30     # info of a root: area | touches_border << 30
 CC_MAX_DIM = 16384     # h, w of the connected-component entry points
 LESION_STATE_EXTRA = 4   # images, ignored, invalid, updates behind [classes][4]
@@ -265,6 +275,11 @@ SIGNATURES = {
     "oct_cc_label": (c_int, [C.POINTER(CcDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oct_cc_filter": (c_int, [C.POINTER(CcDesc), C.POINTER(CcRules), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oct_lesion_eval_update": (c_int, [C.POINTER(CcDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_dt_workspace_bytes": (c_size_t, [C.POINTER(DtDesc)]),
+    "oct_dt_block": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
+    "oct_dt_squared": (c_int, [C.POINTER(DtDesc), C.POINTER(C.c_int32), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_dt_weight_map": (c_int, [C.POINTER(DtDesc), C.POINTER(C.c_int32), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "oct_dt_signed": (c_int, [C.POINTER(DtDesc), C.POINTER(C.c_int32), c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
