@@ -979,6 +979,70 @@ int oct_dt_weight_map(const OctDtDesc* d, const int32_t* planes, const void* map
                       void* workspace, void* stream);
 int oct_dt_signed(const OctDtDesc* d, const int32_t* class_ids, const void* map, float* out, void* workspace, void* stream);
 
+/* Layer surfaces (library 0.2.2, same OCT_VERSION): the K - 1 ordered boundary rows per A-scan between K classes listed top to
+ * bottom, from a class map [images][h][w] (uint8: elem 0, int64: elem 2) or from scores [images][classes][h][w] (NCHW; fp32:
+ * elem 3, bf16: elem 4, widened to fp32 first).  Exact integers: every result is a pure function of the inputs.
+ *   order     K distinct classes, 2 <= K <= OCT_SURF_MAX_K, top to bottom
+ *   free      map: a value not in order, equal to ignore_index (has_ignore) or outside [0, classes);  scores: any channel NaN.
+ *             A free pixel costs nothing wherever a surface passes
+ *   u_j(y,x)  j = 0..K-1.  map: 0 on a free pixel or where the class is order[j], else 1.  scores: with m the maximum over ALL
+ *             channels, v = (m - z[order[j]]) * scale + 0.5 in fp32, every operation rounded on its own (no FMA), the
+ *             difference taken as 0 where z == m;  u_j = floor(v) if v < qmax + 1, else qmax;  0 on a free pixel
+ *   surface k k = 1..K-1 splits order[:k] | order[k:]:  d_k(y,x) = min_{j<k} u_j - min_{j>=k} u_j,
+ *             N_k(x,s) = sum_{y<s} d_k(y,x) for s = 0..h (the rows y < s lie above the surface)
+ *   path      s_k(0..w-1) with |s_k(x+1) - s_k(x)| <= max_step minimising sum_x N_k(x, s_k(x)), chosen by exactly
+ *               A(0,s) = N(0,s);  A(x,s) = N(x,s) + min A(x-1,t) over |t-s| <= max_step, 0 <= t <= h;  P(x,s) = the SMALLEST
+ *               such t;  s(w-1) = the smallest argmin of A(w-1,.);  s(x-1) = P(x, s(x))
+ *             max_step = -1 (none): s(x) = the smallest argmin of N(x,.)
+ *   ordering  afterwards s_k <- max(s_k, s_{k-1}) down the surfaces (a tie-breaker: DESIGN.md)
+ *   painted   out(y,x) = order[#{k : s_k(x) <= y}]; where the input class (scores: the arg-max, first maximum, the first NaN
+ *             beats everything) is listed in `keep` (disjoint from order) the pixel keeps it
+ *
+ * oct_surf_extract(d, order, in, surfaces, workspace, stream)
+ *   order     HOST memory, int32 [d->k]
+ *   surfaces  int32 [images][k-1][w], WRITTEN, values in [0, h]
+ *   workspace oct_surf_workspace_bytes(d) bytes on the device, 16-byte aligned, contents irrelevant before and after: with
+ *             cells = images*(k-1)*w*(h+1) and A(x) = x rounded up to 256, A(4*cells) + A(cells): N as int32 [image][k][x][s]
+ *             and P as int8 offsets t - s.  0 (and no workspace is read) with max_step = -1; 0 too for a descriptor the entry
+ *             points reject
+ * oct_surf_paint(d, order, keep, in, surfaces, out, stream)
+ *   keep      HOST memory, int32 [d->nkeep], null with nkeep = 0
+ *   in        read only where nkeep > 0 (scores) / always validated (maps: it fixes the output's element)
+ *   out       [images][h][w], the map's element, int64 for scores, WRITTEN; may be `in` itself for a map (one read, one write per
+ *             pixel by the same thread)
+ * oct_surf_error_update(d, target_surf, pred_surf, valid, state, stream)
+ *   uses d->images, d->w, d->k only.  valid: uint8 [images][w] or null (every column).  state: int64 [k-1][5], ADDED TO:
+ *   count, sum |e|, sum e, sum e^2 and (atomicMax) max |e| with e = pred - target over the valid columns.  The rows are
+ *   expected in [0, OCT_SURF_MAX_H], as oct_surf_extract writes them: the sums are then exact; they are not range-checked
+ *
+ * Refused: h > OCT_SURF_MAX_H; qmax * h * w >= 2^31 (a map counts as qmax = 1): every path cost fits int32; max_step outside
+ * -1..OCT_SURF_MAX_STEP; scale not finite and positive; qmax outside 1..255; order / keep entries outside [0, classes), repeated
+ * in order, or shared between the two.  Launches: cost (unary bytes through LDS, a wave scan per column and surface; with
+ * max_step = -1 it keeps each column's arg-min, writes `surfaces` and nothing else runs) -> search (one workgroup per (image,
+ * surface), A in two LDS rows, one barrier per column, then the walk back) -> ordering.  No allocation, no host
+ * synchronisation, no floating-point atomics, only `stream`; images == 0 is a no-op. */
+#define OCT_SURF_MAX_K 16
+#define OCT_SURF_MAX_H 4095
+#define OCT_SURF_MAX_STEP 32
+typedef struct {
+  int images, h, w, classes; /* images = product of all leading dims; classes = channels of scores; 1 <= classes <= 16 */
+  int elem;                  /* 0 uint8 map, 2 int64 map, 3 fp32 scores, 4 bf16 scores */
+  int k;                     /* entries of order */
+  int max_step;              /* -1: none */
+  int has_ignore;            /* maps */
+  int nkeep;                 /* entries of keep (oct_surf_paint) */
+  int qmax;                  /* scores: 1..255 */
+  float scale;               /* scores: finite, > 0 */
+  int reserved;
+  int64_t ignore_index;
+} OctSurfDesc;
+size_t oct_surf_workspace_bytes(const OctSurfDesc* d);
+int oct_surf_extract(const OctSurfDesc* d, const int32_t* order, const void* in, int32_t* surfaces, void* workspace, void* stream);
+int oct_surf_paint(const OctSurfDesc* d, const int32_t* order, const int32_t* keep, const void* in, const int32_t* surfaces, void* out,
+                   void* stream);
+int oct_surf_error_update(const OctSurfDesc* d, const int32_t* target_surf, const int32_t* pred_surf, const uint8_t* valid,
+                          int64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

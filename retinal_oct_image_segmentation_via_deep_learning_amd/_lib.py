@@ -109,12 +109,20 @@ class DtDesc(C.Structure):           # struct OctDtDesc
                [("ignore_index", C.c_int64)]
 
 
+class SurfDesc(C.Structure):         # struct OctSurfDesc
+    _fields_ = [(k, c_int) for k in ("images", "h", "w", "classes", "elem", "k", "max_step", "has_ignore", "nkeep", "qmax")] + \
+               [("scale", c_float), ("reserved", c_int), ("ignore_index", C.c_int64)]
+
+
 CC_OP_LABEL, CC_OP_FILTER, CC_OP_LESION = range(3)   # OCT_CC_OP_*
 DT_FAR = 1 << 30       # OCT_DT_FAR: the squared distance where an image has no site of the plane
 DT_MAX_PLANES = 64     # OCT_DT_MAX_PLANES; oct_dt_signed takes half as many classes
 DT_MAX_DIM = 16384     # h, w of the distance-map entry points
 DT_BOUNDARY, DT_CLASS, DT_OTHER = range(3)   # OCT_DT_* plane kinds
 DT_OP_SQUARED, DT_OP_WEIGHT, DT_OP_SIGNED = range(3)   # OCT_DT_OP_*
+SURF_MAX_K, SURF_MAX_H, SURF_MAX_STEP = 16, 4095, 32   # OCT_SURF_MAX_*
+SURF_F32, SURF_BF16 = 3, 4   # OctSurfDesc.elem of scores (class maps: 0 uint8, 2 int64)
+SURF_STATE_FIELDS = 5  # count, sum |e|, sum e, sum e^2, max |e| per surface
 CC_BORDER_BIT = 30     # info of a root: area | touches_border << 30
 CC_MAX_DIM = 16384     # h, w of the connected-component entry points
 LESION_STATE_EXTRA = 4   # images, ignored, invalid, updates behind [classes][4]
@@ -280,6 +288,10 @@ SIGNATURES = {
     "oct_dt_squared": (c_int, [C.POINTER(DtDesc), C.POINTER(C.c_int32), c_void_p, c_void_p, c_void_p, c_void_p]),
     "oct_dt_weight_map": (c_int, [C.POINTER(DtDesc), C.POINTER(C.c_int32), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "oct_dt_signed": (c_int, [C.POINTER(DtDesc), C.POINTER(C.c_int32), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_surf_workspace_bytes": (c_size_t, [C.POINTER(SurfDesc)]),
+    "oct_surf_extract": (c_int, [C.POINTER(SurfDesc), C.POINTER(C.c_int32), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_surf_paint": (c_int, [C.POINTER(SurfDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oct_surf_error_update": (c_int, [C.POINTER(SurfDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,12 +1,12 @@
 """Streaming validation metrics with the state on the device.
 
 A validation loop scores batch after batch; `Metrics.evaluate(y_true, y_pred, classes=C)` reads its counts back per batch and
-knows neither a C x C confusion matrix nor ignore_index.  The four evaluators here keep their result on the device: update()
+knows neither a C x C confusion matrix nor ignore_index.  The evaluators here keep their result on the device: update()
 launches on the stream of its tensors' device and never synchronises, compute() is the only call that reads back, and there
 is no CPU fallback.  What they share is written once: `_Evaluator` (the device= argument and the three device rules of
 _bind), `_StateEvaluator` (one summable int64 state: state, reset, all_reduce, _host_state -- SegEvaluator, ScoreEvaluator,
-LesionEvaluator; BoundaryEvaluator's records are per image and not summable) and the plain functions below it for class-map
-pairs, image chunks under a workspace limit, the cached workspace and the model dispatch of update_model.
+LesionEvaluator, SurfaceEvaluator; BoundaryEvaluator's records are per image and not summable) and the plain functions below
+it for class-map pairs, image chunks under a workspace limit, the cached workspace and the model dispatch of update_model.
 
 Confusion matrix and thickness (csrc/seg_eval.hip, oct_seg_eval_update): `SegEvaluator` ADDS to one int64 buffer per update
 
@@ -53,6 +53,10 @@ Lesion-wise scores (csrc/components.hip, oct_lesion_eval_update): `LesionEvaluat
 (same value, 4- or 8-neighbours; postprocess.py has the labelling itself and the cleanup filter) and keeps, per class, four
 int64 counts on the device -- target components, predicted components, detected, confirmed; sensitivity, precision and F1 per
 lesion follow from them in `lesion_metrics_from_state` (numpy, float64).
+
+Surface position error (csrc/surfaces.hip, oct_surf_error_update): `SurfaceEvaluator` compares two sets of layer surfaces
+(surfaces.py: one boundary row per A-scan and interface) and keeps, per surface, five int64 values on the device -- columns,
+sum |e|, sum e, sum e^2, max |e|; mean absolute, signed and RMS error in pixels follow in `surface_metrics_from_state`.
 
 Deviations from the reference's Metrics/Contour_based_metrics.py, by decision: it scores only the FIRST contour find_contours
 returns (order-dependent) and counts the first vertex of a closed contour twice; here every contour counts and every vertex
@@ -848,3 +852,119 @@ class LesionEvaluator(_StateEvaluator):
         """The only call that synchronises: lesion_metrics_from_state on the state.  `updates` counts kernel calls, one per
         chunk of an update."""
         return lesion_metrics_from_state(self._host_state(), self.classes)
+
+
+# ---- layer surfaces: boundary position error per surface -----------------------------------------------------------------------
+SURFACE_FIELDS = ("count", "sum_abs", "sum_signed", "sum_sq", "max_abs")
+
+
+def surface_state_size(surfaces: int) -> int:
+    return surfaces * len(SURFACE_FIELDS)
+
+
+def surface_metrics_from_state(state, surfaces: int) -> dict:
+    """The boundary position errors of SurfaceEvaluator from its int64 state [surfaces][count, sum |e|, sum e, sum e^2, max |e|]
+    (numpy float64, no GPU), e = predicted - target row in pixels, per surface:
+      columns int64;  mean_abs_error = sum |e| / columns, mean_signed_error = sum e / columns (positive: predicted too deep),
+      rmse = sqrt(sum e^2 / columns), max_abs_error -- NaN where a surface has no column;
+      mean_mean_abs_error, mean_mean_signed_error, mean_rmse, mean_max_abs_error: their means over the surfaces that have
+      columns (NaN without one)."""
+    _check_int("surfaces", surfaces, 1, L.SURF_MAX_K - 1)
+    s = _int_state(state, surface_state_size(surfaces), f"{surfaces} surfaces").reshape(surfaces, len(SURFACE_FIELDS))
+    n = s[:, 0].copy()
+    has = n > 0
+    den = np.where(has, n, 1).astype(np.float64)
+    nan = np.float64("nan")
+    res = {
+        "columns": n,
+        "mean_abs_error": np.where(has, s[:, 1] / den, nan),
+        "mean_signed_error": np.where(has, s[:, 2] / den, nan),
+        "rmse": np.where(has, np.sqrt(s[:, 3] / den), nan),
+        "max_abs_error": np.where(has, s[:, 4].astype(np.float64), nan),
+    }
+    for k in ("mean_abs_error", "mean_signed_error", "rmse", "max_abs_error"):
+        res["mean_" + k] = float(res[k][has].mean()) if has.any() else float("nan")
+    return res
+
+
+class SurfaceEvaluator(_StateEvaluator):
+    """Boundary position error per layer surface -- mean absolute, signed and RMS, in pixels: the headline number of the
+    layer-segmentation papers -- accumulated on the device (csrc/surfaces.hip, oct_surf_error_update).  The int64 state is
+
+        [surfaces][count, sum |e|, sum e, sum e^2, max |e|],   e = predicted - target row, over the valid columns
+
+        layers = LayerSurfaces(classes=9, order=range(8), max_step=1, ignore_index=255)
+        ev = SurfaceEvaluator(surfaces=7)
+        for x, y in loader:
+            ev.update_maps(y, model.predict(x), layers)     # or ev.update(target_surfaces, layers.from_model(model, x))
+        m = ev.compute()                                    # the one synchronisation; m["mean_abs_error"], m["rmse"], ..."""
+
+    def __init__(self, surfaces, device=None):
+        _check_int("surfaces", surfaces, 1, L.SURF_MAX_K - 1)
+        super().__init__(device, surface_state_size(surfaces))
+        self.surfaces = surfaces
+
+    def update(self, target_surfaces, pred_surfaces, valid=None):
+        """Two int32 surface tensors of one shape (..., surfaces, W) -- what LayerSurfaces.extract returns -- and optionally
+        `valid` (..., W), bool / uint8: the columns that count (all of them without it).  The rows are expected in
+        [0, 4095], the range extract writes: the int64 sums are then exact.  The values stay on the device and are not
+        range-checked (that would synchronise); rows made up with |e| near 2^32 would wrap the sum of squares."""
+        from .surfaces import _check_surfaces
+        if not torch.is_tensor(target_surfaces):
+            raise TypeError(f"target_surfaces must be a torch tensor, got {type(target_surfaces).__name__}")
+        if target_surfaces.dim() < 2 or target_surfaces.shape[-2] != self.surfaces or target_surfaces.shape[-1] < 1:
+            raise RuntimeError(f"target_surfaces must have shape (..., {self.surfaces}, W >= 1), got {tuple(target_surfaces.shape)}")
+        w = target_surfaces.shape[-1]
+        images = target_surfaces.numel() // (self.surfaces * w)
+        device = target_surfaces.device
+        t = _check_surfaces(target_surfaces, images, self.surfaces + 1, w, device, "target_surfaces")
+        p = _check_surfaces(pred_surfaces, images, self.surfaces + 1, w, device, "pred_surfaces")
+        if valid is not None:
+            if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8):
+                raise TypeError("valid must be a bool / uint8 tensor, got "
+                                f"{valid.dtype if torch.is_tensor(valid) else type(valid).__name__}")
+            if valid.numel() != images * w or valid.shape[-1] != w:
+                raise RuntimeError(f"valid must have shape (..., {w}) for {images} images, got {tuple(valid.shape)}")
+            if valid.device != device:
+                raise RuntimeError(f"valid is on {valid.device}, the surfaces on {device}")
+            valid = valid.to(torch.uint8).contiguous()
+        state = self._state_on(device)
+        if images == 0:
+            return self
+        desc = L.SurfDesc(images, 1, w, 1, 0, self.surfaces + 1, -1, 0, 0, 1, 1.0, 0, 0)
+        L.check(L.lib().oct_surf_error_update(C.byref(desc), t.data_ptr(), p.data_ptr(), L.ptr(valid), state.data_ptr(),
+                                              torch.cuda.current_stream(device).cuda_stream), "oct_surf_error_update")
+        return self
+
+    def update_maps(self, target_map, pred_map, extractor):
+        """Two integer class maps of one shape (..., H, W) through `extractor` (a LayerSurfaces over surfaces + 1 classes): the
+        predicted surfaces with its settings, the target's with max_step=None -- for a topologically valid target exactly its
+        boundaries.  With the extractor's ignore_index a column counts where any of its target pixels is not ignore_index."""
+        from .surfaces import LayerSurfaces
+        if not isinstance(extractor, LayerSurfaces):
+            raise TypeError(f"extractor must be a LayerSurfaces, got {type(extractor).__name__}")
+        if len(extractor.order) != self.surfaces + 1:
+            raise RuntimeError(f"the extractor orders {len(extractor.order)} classes, the evaluator has {self.surfaces} surfaces")
+        target_map, pred_map, _ = _class_map_pair(target_map, pred_map)
+        valid = None
+        if extractor.ignore_index is not None:
+            valid = (target_map != extractor.ignore_index).any(-2)
+        return self.update(extractor.unconstrained().extract(target_map), extractor.extract(pred_map), valid)
+
+    def all_reduce(self, group=None):
+        """Sum the counts and sums over the ranks of `group` and take the maximum of max |e| (a SUM and a MAX all-reduce)."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return self
+        if self.state is None:
+            self._state_on(self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device()))
+        rows = self.state.view(self.surfaces, len(SURFACE_FIELDS))
+        worst = rows[:, 4].clone()
+        dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(worst, op=dist.ReduceOp.MAX, group=group)
+        rows[:, 4] = worst
+        return self
+
+    def compute(self) -> dict:
+        """The only call that synchronises: surface_metrics_from_state on the state."""
+        return surface_metrics_from_state(self._host_state(), self.surfaces)
